@@ -1,10 +1,21 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark: batched negacyclic poly-mults/s on N MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config cfg3|cfg2] [--rows R | --global-batch B]
+    python bench.py --gpus N --steps K --warmup W [--config cfg3|cfg2] [--rows R | --global-batch B] [--dump-outputs DIR] [--full]
 
 A step = one pass of the hot path (tn_poly_mult_dev, fused kernel) over this rank's block of synthetic
 polynomial pairs, inputs resident in HBM.  Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline figure needs: set-up, device spin-up, the W warm-up steps, the K timed steps,
+the outputs if --dump-outputs is given, and the line (metric, value, unit, higher_is_better, dtype, ms_per_step = wall
+milliseconds of one timed step, and what the run was).  --full adds everything else: the bit-exactness gate, the `roofline`
+from a separate HIP-event timing of the kernel, the CPU oracle check and `cpu_baseline`, and the optional legs --latency,
+--strong-point and --scatter-gather, which need it.
+
+--dump-outputs DIR: after the timed steps, a fixed seeded sample of what the last step returned (dump_rows(): at most 512
+rows of c over all ranks), each word split into its upper and lower 32 bits as float64 (exact; a 60-bit word is not) ->
+DIR/c_hi.npy, DIR/c_lo.npy (with N>1: c_hi_rank<r>.npy, c_lo_rank<r>.npy per rank).  Inputs depend only on the arguments,
+so two builds can be compared file for file.  At most 32 MiB.
 
 Workloads (BASELINE.json `configs`):
   cfg3 (default)  n=4096, q=2^60-2^14+1, u64 — the configuration the metric is quoted on.
@@ -19,16 +30,16 @@ N>1 is launched by `python -m torch.distributed.run --nproc-per-node N ... bench
 WORLD_SIZE/MASTER_* from the environment); called WITHOUT that launcher, `--gpus N` starts the N ranks itself
 (fresh child processes, before anything touches the GPU) and exits with their status.
 
-Extra objects on the line:
+Extra objects on a --full line:
   roofline      — algorithmic bytes (3*n*w B per product: read a, read b, write c) per launch /
                   mean launch duration measured with HIP events on the stream the kernel runs on.
   cpu_baseline  — the reference's own benchmark binary (oracle/_ref, kind "reference") or this repo's C restatement
                   (kind "port"), timed on this box's host cores for a bounded sample; CPU model and core count stated.
-  control_plane — "rccl" | "gloo" | "none": what carried the barrier / max-reduce, and how many ranks it counted.
-The result is gated on bit-exactness first (every rank): the first global row must reproduce the checksum the reference
-C++ benchmark prints and sampled rows must equal the on-device O(n^2) direct product; in the cpu_baseline leg (N=1)
-64 sampled rows are also compared with the CPU oracle.  Any mismatch aborts the run.
-Order: one checked pass, a fixed device spin-up (40 untimed launches: the shader clock needs ~0.1 s to settle after
+  parity        — --full gates the result on bit-exactness first (every rank): the first global row must reproduce the
+                  checksum the reference C++ benchmark prints and sampled rows must equal the on-device O(n^2) direct product;
+                  in the cpu_baseline leg (N=1) 64 sampled rows are also compared with the CPU oracle.  Any mismatch aborts the run.
+Every line has control_plane — "rccl" | "gloo" | "none": what carried the barrier / max-reduce, and how many ranks it counted.
+Order: (--full: one checked pass), a fixed device spin-up (40 untimed launches: the shader clock needs ~0.1 s to settle after
 idle), the W warm-up steps, then exactly K timed steps between barriers — so the result does not depend on K or W.
 """
 import argparse
@@ -51,6 +62,7 @@ HBM_PEAK_GBS = 8000.0                   # MI355X_MICROARCH.md: HBM3E 8.0 TB/s sp
 SPINUP = 40                             # untimed launches before the W warm-up steps (setup: the shader clock settles ~0.1 s after idle); on the line
 SPINUP_SECONDS = 0.15                   # ... and at least this long: 40 launches of a short workload (cfg2: 23 us each) end long before the clock has
                                         # settled (measured: 23.5-24.5 us per step after 1 ms of launches, 20.4 us after 45 ms, profiles/r3_cfg2_short_launch_ab.txt)
+DUMP_ROWS = 512                         # --dump-outputs: rows of c sampled over all ranks (cfg3: 512 x 4096 words x 2 float64 halves = 32 MiB)
 
 # parameter sets: SURVEY.md §8 table; checksums: what the reference benchmark prints for make_poly(1) x make_poly(2)
 CONFIGS = {
@@ -107,6 +119,27 @@ def verify(plan, a, b, c, first_global_row, cfg):
     if not torch.equal(direct, sc):
         raise SystemExit("PARITY FAILURE: sampled rows differ from the direct O(n^2) product")
     return len(idx), int(sums[0])
+
+
+def dump_rows(rows, world):
+    """Local row indices (sorted) of the fixed, seeded sample of a rank's block that --dump-outputs writes."""
+    import numpy as np
+    k = min(rows, max(1, DUMP_ROWS // world))
+    return np.sort(np.random.default_rng(0).choice(rows, size=k, replace=False))
+
+
+def dump_outputs(directory, plan, c, rank, world):
+    """--dump-outputs: the sampled rows of c as the last timed step left them, every word split into its upper and lower
+    32 bits (float64 holds each half exactly, a 60-bit word it does not) -> c_hi.npy, c_lo.npy (N>1: one pair per rank)."""
+    import numpy as np
+    import torch
+    plan.synchronize()
+    idx = dump_rows(c.shape[0], world)
+    words = plan.to_host(c[torch.from_numpy(idx).to(c.device)]).astype(np.uint64)
+    suffix = "" if world == 1 else f"_rank{rank}"
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, f"c_hi{suffix}.npy"), (words >> np.uint64(32)).astype(np.float64))
+    np.save(os.path.join(directory, f"c_lo{suffix}.npy"), (words & np.uint64(0xFFFFFFFF)).astype(np.float64))
 
 
 def oracle_check(plan, a, b, c, cfg):
@@ -277,18 +310,28 @@ def parse_args(argv=None):
     ap.add_argument("--rows", type=int, default=None, help="rows per GPU, weak scaling (default: see the module docstring)")
     ap.add_argument("--global-batch", type=int, default=None, help="rows of ONE global batch split over the ranks, strong scaling")
     ap.add_argument("--variant", default="fused")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write a fixed seeded sample of the last step's products to DIR/*.npy (module docstring)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the parity gate, the roofline kernel timing, the CPU oracle check and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU oracle check and CPU baseline")
     # both off by default: they launch the SAME kernel on other batch sizes, and the default command's rocprofv3 --kernel-trace --stats
     # summary must show that kernel's average launch duration for the bench workload alone (profiles/r3_f_kernel_stats.csv)
-    ap.add_argument("--latency", action="store_true", help="N=1: add the small-batch latency block (1 / 16 / 256 pairs device-resident, 1 pair host-buffer)")
+    ap.add_argument("--latency", action="store_true",
+                    help="with --full, N=1: add the small-batch latency block (1 / 16 / 256 pairs device-resident, 1 pair host-buffer)")
     ap.add_argument("--strong-point", action="store_true",
-                    help="N=1, cfg3: add the N = 1 point of the strong-scaling curve (the whole 2^20-pair batch of BASELINE configs[3] on this GPU)")
+                    help="with --full, N=1, cfg3: add the N = 1 point of the strong-scaling curve (the whole 2^20-pair batch of BASELINE configs[3] on this GPU)")
     ap.add_argument("--allow-gloo", action="store_true",
                     help="N>1: if the RCCL control plane cannot come up, run the barrier / max-reduce over gloo instead of failing")
     ap.add_argument("--scatter-gather", type=int, default=0, metavar="ROWS",
-                    help="N>1 only, off by default: also time the OPTIONAL scatter of a, b from rank 0 and gather of c "
+                    help="with --full, N>1 only: also time the OPTIONAL scatter of a, b from rank 0 and gather of c "
                          "(tiny_ntt_amd.dist, point-to-point over RCCL/xGMI) on ROWS rows per rank; reported separately, never part of value")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full and (args.latency or args.strong_point or args.scatter_gather > 0):
+        ap.error("--latency, --strong-point and --scatter-gather are legs of a --full run")
+    return args
 
 
 def main():
@@ -358,10 +401,11 @@ def main():
     c = torch.empty_like(a)
     plan.synchronize()
 
-    # correctness first (one pass, checked), so that nothing idles the device between warm-up and the timed steps
-    plan.poly_mult(a, b, variant=args.variant, out=c, stream=S)
-    plan.synchronize()
-    checked, first_sum = verify(plan, a, b, c, first_row, cfg)
+    if args.full:
+        # correctness first (one pass, checked), so that nothing idles the device between warm-up and the timed steps
+        plan.poly_mult(a, b, variant=args.variant, out=c, stream=S)
+        plan.synchronize()
+        checked, first_sum = verify(plan, a, b, c, first_row, cfg)
     # device spin-up (part of setup, like plan creation and data generation): after idle the first ~0.1 s of launches run
     # below the steady shader clock, whatever W the caller asks for
     spin_launches, t_spin = 0, time.perf_counter()
@@ -389,17 +433,23 @@ def main():
     elapsed_local = elapsed = time.perf_counter() - t0
     barrier()
     elapsed = tdist.max_over_ranks(elapsed, red_dev)
+    if args.dump_outputs:                                      # before anything else launches on c
+        dump_outputs(args.dump_outputs, plan, c, rank, world)
 
-    # dominant kernel: mean launch duration with HIP events on the plan's stream (the one the timed loop used)
-    my_kernel_ms = plan.time_poly_mult(a, b, c, max(args.steps, 5), args.variant)
-    kernel_ms = tdist.max_over_ranks(my_kernel_ms, red_dev)
-    per_rank = tdist.gather_floats([float(rows), my_kernel_ms, elapsed_local * 1e3 / args.steps], red_dev)   # a straggler shows here
+    step_ms = [float(rows), elapsed_local * 1e3 / args.steps]
+    if args.full:
+        # dominant kernel: mean launch duration with HIP events on the plan's stream (the one the timed loop used)
+        my_kernel_ms = plan.time_poly_mult(a, b, c, max(args.steps, 5), args.variant)
+        kernel_ms = tdist.max_over_ranks(my_kernel_ms, red_dev)
+        step_ms.append(my_kernel_ms)
+    per_rank = tdist.gather_floats(step_ms, red_dev)           # a straggler shows here
     max_rows = int(tdist.max_over_ranks(rows, red_dev))        # the rank that sets the time owns the largest block
-    achieved = max_rows * bytes_per_product / (kernel_ms * 1e-3) / 1e9
 
-    # the timed launches must have left the checked result in place
-    _, last_sum = verify(plan, a, b, c, first_row, cfg)
-    parity_ok = last_sum == first_sum
+    if args.full:
+        achieved = max_rows * bytes_per_product / (kernel_ms * 1e-3) / 1e9
+        # the timed launches must have left the checked result in place
+        _, last_sum = verify(plan, a, b, c, first_row, cfg)
+        parity_ok = last_sum == first_sum
 
     sg = None
     if args.scatter_gather > 0 and world > 1:
@@ -437,7 +487,7 @@ def main():
     # HBM bytes per launch from separate rocprofv3 --pmc passes (tools/gpu_pmc.sh): only if taken on THIS library build
     traffic, traffic_note = None, None
     tpath = os.path.join(ROOT, "profiles", "traffic_latest.json")
-    if os.path.exists(tpath):
+    if args.full and os.path.exists(tpath):
         try:
             with open(tpath) as f:
                 tj = json.load(f)
@@ -451,30 +501,6 @@ def main():
     total = sp["global_batch"] * args.steps
     value = total / elapsed
     if rank == 0:
-        base, oracle_rows, latency, curve = None, 0, None, None
-        if not (args.no_cpu_baseline or world > 1):          # the CPU leg, part 1: the oracle as checker on sampled rows
-            oracle_rows = oracle_check(plan, a, b, c, cfg)
-        if world == 1 and args.latency:
-            latency = latency_block(plan, a, b, c, args.variant)
-        if world == 1 and args.config == "cfg3" and args.strong_point:
-            # the N = 1 point of the strong-scaling curve (BASELINE configs[3]: ONE batch of 2^20 pairs over 1/2/4/8 GPUs): the whole
-            # batch on this GPU (96 GiB of a, b, c), same kernel, a few launches; N > 1 lines divide THIS batch
-            try:
-                del a, b, c
-                torch.cuda.empty_cache()
-                gb = cfg["global_batch"]
-                A = plan.fill_lcg(gb, 1, 2, stream=S); B = plan.fill_lcg(gb, 2, 2, stream=S); C = torch.empty_like(A)
-                plan.time_poly_mult(A, B, C, 2, args.variant)
-                ms = plan.time_poly_mult(A, B, C, 5, args.variant)
-                ok = int(plan.checksum_rows(C[:1], stream="plan")[0]) == cfg["checksum_row0"]
-                curve = {"global_batch": gb, "n_gpus": 1, "value": round(gb / (ms * 1e-3), 1), "ms_per_step": round(ms, 3),
-                         "row0_matches_reference": ok, "command": f"python bench.py --gpus 1 --global-batch {gb}  (or: python bench.py --strong-point)"}
-                del A, B, C
-                torch.cuda.empty_cache()
-            except Exception as e:                                 # e.g. a smaller GPU: the point is optional
-                curve = {"skipped": f"{type(e).__name__}: {str(e)[:200]}"}
-        if not (args.no_cpu_baseline or world > 1):          # the CPU leg, part 2: the reference binary as baseline
-            base = cpu_baseline(cfg)
         line = {
             "metric": cfg["metric"],
             "value": round(value, 1),
@@ -488,6 +514,7 @@ def main():
             "vs_baseline": None,
             "dtype": cfg["dtype"],
             "data": "synthetic",
+            "full": args.full,
             "config": {"workload": f"{cfg['label']}, global batch {sp['global_batch']} = {rows} rows on this GPU"
                                    f"{'' if world == 1 else ' (contiguous row blocks, rows_g = batch/N)'}, LCG-seeded rows resident in HBM "
                                    f"({cfg['baseline_cfg'] if world == 1 else 'BASELINE configs[3]' if args.config == 'cfg3' and sp['scaling'] == 'strong' else cfg['baseline_cfg'] + ' per GPU'})",
@@ -501,22 +528,45 @@ def main():
             "integer_work": {"modmuls_per_product": modmuls, "modmuls_per_s": round(value * modmuls, 1)},
             "control_plane": control_plane,
             "control_plane_ranks": counted,
-            "parity": {"first_row_checksum_device": first_sum, "reference_row0_checksum": cfg["checksum_row0"],
-                       "row0_matches_reference": (first_sum == cfg["checksum_row0"]) if first_row == 0 else None,
-                       "rows_compared_with_direct_product_on_device": checked,
-                       "rows_compared_with_cpu_oracle": oracle_rows,
-                       "bit_exact": bool(parity_ok and (first_row != 0 or first_sum == cfg["checksum_row0"]))},
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
-                         "kernel": plan.kernel_name(args.variant), "kernel_ms": round(kernel_ms, 5),
-                         "algorithmic_bytes_per_launch": max_rows * bytes_per_product},
-            "cpu_baseline": base,
-            "latency": latency,
-            "strong_scaling_n1_point": curve,
-            "per_rank": {"rows": [int(r[0]) for r in per_rank], "kernel_ms": [round(r[1], 5) for r in per_rank],
-                         "ms_per_step": [round(r[2], 5) for r in per_rank]},
+            "per_rank": {"rows": [int(r[0]) for r in per_rank], "ms_per_step": [round(r[1], 5) for r in per_rank]},
             "spinup_launches": spin_launches,
         }
+        if args.full:
+            base, oracle_rows, latency, curve = None, 0, None, None
+            if not (args.no_cpu_baseline or world > 1):          # the CPU leg, part 1: the oracle as checker on sampled rows
+                oracle_rows = oracle_check(plan, a, b, c, cfg)
+            if world == 1 and args.latency:
+                latency = latency_block(plan, a, b, c, args.variant)
+            if world == 1 and args.config == "cfg3" and args.strong_point:
+                # the N = 1 point of the strong-scaling curve (BASELINE configs[3]: ONE batch of 2^20 pairs over 1/2/4/8 GPUs): the whole
+                # batch on this GPU (96 GiB of a, b, c), same kernel, a few launches; N > 1 lines divide THIS batch
+                try:
+                    del a, b, c
+                    torch.cuda.empty_cache()
+                    gb = cfg["global_batch"]
+                    A = plan.fill_lcg(gb, 1, 2, stream=S); B = plan.fill_lcg(gb, 2, 2, stream=S); C = torch.empty_like(A)
+                    plan.time_poly_mult(A, B, C, 2, args.variant)
+                    ms = plan.time_poly_mult(A, B, C, 5, args.variant)
+                    ok = int(plan.checksum_rows(C[:1], stream="plan")[0]) == cfg["checksum_row0"]
+                    curve = {"global_batch": gb, "n_gpus": 1, "value": round(gb / (ms * 1e-3), 1), "ms_per_step": round(ms, 3),
+                             "row0_matches_reference": ok, "command": f"python bench.py --gpus 1 --global-batch {gb}  (or: python bench.py --full --strong-point)"}
+                    del A, B, C
+                    torch.cuda.empty_cache()
+                except Exception as e:                                 # e.g. a smaller GPU: the point is optional
+                    curve = {"skipped": f"{type(e).__name__}: {str(e)[:200]}"}
+            if not (args.no_cpu_baseline or world > 1):          # the CPU leg, part 2: the reference binary as baseline
+                base = cpu_baseline(cfg)
+            line["parity"] = {"first_row_checksum_device": first_sum, "reference_row0_checksum": cfg["checksum_row0"],
+                              "row0_matches_reference": (first_sum == cfg["checksum_row0"]) if first_row == 0 else None,
+                              "rows_compared_with_direct_product_on_device": checked,
+                              "rows_compared_with_cpu_oracle": oracle_rows,
+                              "bit_exact": bool(parity_ok and (first_row != 0 or first_sum == cfg["checksum_row0"]))}
+            line["roofline"] = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
+                                "kernel": plan.kernel_name(args.variant), "kernel_ms": round(kernel_ms, 5),
+                                "algorithmic_bytes_per_launch": max_rows * bytes_per_product}
+            line["cpu_baseline"], line["latency"], line["strong_scaling_n1_point"] = base, latency, curve
+            line["per_rank"]["kernel_ms"] = [round(r[2], 5) for r in per_rank]
         if traffic_note:
             line["roofline"]["traffic_note"] = traffic_note
         if sg is not None:

@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -71,3 +72,25 @@ def test_gpus_flag_without_a_launcher_starts_that_many_ranks():
     assert r.returncode != 0
     assert r.stderr.count("needs a HIP device") == 2, r.stderr
     assert r.stdout.strip() == ""
+
+
+def test_plain_run_is_the_default_and_the_extra_legs_need_full():
+    args = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (args.steps, args.warmup, args.full, args.dump_outputs) == (7, 2, False, None)
+    full = bench.parse_args(["--full", "--latency", "--strong-point", "--dump-outputs", "out"])
+    assert full.full and full.latency and full.strong_point and full.dump_outputs == "out"
+    for argv in (["--latency"], ["--strong-point"], ["--scatter-gather", "8"], ["--steps", "0"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(argv)
+
+
+@pytest.mark.parametrize("world", [1, 2, 8])
+def test_dump_sample_is_fixed_bounded_and_within_the_block(world):
+    rows = 65536 // world
+    idx = bench.dump_rows(rows, world)
+    assert np.array_equal(idx, bench.dump_rows(rows, world))                  # seeded: the same rows every run
+    assert len(idx) == bench.DUMP_ROWS // world and len(set(idx.tolist())) == len(idx)
+    assert np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < rows
+    # every rank writes two float64 halves per sampled word: 32 MiB over all ranks at cfg3, under the 64 MB cap
+    assert world * len(idx) * bench.CONFIGS["cfg3"]["n"] * 2 * 8 <= 32 * 2 ** 20
+    assert np.array_equal(bench.dump_rows(100, 1), np.arange(100))            # a block smaller than the sample: all of it

@@ -5,9 +5,11 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
-from conftest import ROOT
+import bench
+from conftest import PARAMS, ROOT
 
 pytestmark = pytest.mark.gpu
 
@@ -24,7 +26,7 @@ def run_bench(*args, env=None):
 
 
 def test_single_gpu_line_small_workload():
-    j = run_bench("--steps", "3", "--warmup", "1", "--rows", "2048", "--no-cpu-baseline", "--latency")
+    j = run_bench("--full", "--steps", "3", "--warmup", "1", "--rows", "2048", "--no-cpu-baseline", "--latency")
     assert j["n_gpus"] == 1 and j["dtype"] == "u64" and j["unit"] == "poly-mults/s" and j["higher_is_better"] is True
     assert j["control_plane"] == "none" and j["scaling"] == "weak"
     p = j["parity"]
@@ -38,8 +40,15 @@ def test_single_gpu_line_small_workload():
     assert j["strong_scaling_n1_point"] is None          # only with --strong-point
 
 
-def test_cfg2_line_with_reference_cpu_baseline():
-    j = run_bench("--config", "cfg2", "--steps", "5", "--warmup", "2")
+def test_cfg2_line_with_reference_cpu_baseline(tmp_path, oracle):
+    j = run_bench("--full", "--config", "cfg2", "--steps", "5", "--warmup", "2", "--dump-outputs", str(tmp_path))
+    # a --full run dumps the timed steps' products too; 32-bit words: the upper halves are zero
+    c = dumped_words(tmp_path)
+    rows = bench.dump_rows(4096, 1)
+    n, q, psi = PARAMS["P1024"]
+    assert c.shape == (len(rows), n) == (512, 1024) and int(c.max()) < q
+    r = int(rows[-1])
+    assert np.array_equal(c[-1], oracle.poly_mult(oracle.make_poly(2 * r + 1, n, q), oracle.make_poly(2 * r + 2, n, q), q, psi))
     assert j["dtype"] == "u32" and j["config"]["n"] == 1024 and j["config"]["global_batch"] == 4096
     assert j["roofline"]["algorithmic_bytes_per_launch"] == 4096 * 12288
     assert j["parity"]["bit_exact"] is True and j["parity"]["first_row_checksum_device"] == 15308795525113097448
@@ -51,7 +60,7 @@ def test_cfg2_line_with_reference_cpu_baseline():
 
 
 def test_two_ranks_without_launcher_strong_split_over_gloo():
-    j = run_bench("--gpus", "2", "--steps", "2", "--warmup", "1", "--global-batch", "3000", "--no-cpu-baseline",
+    j = run_bench("--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--global-batch", "3000", "--no-cpu-baseline",
                   env={"BENCH_BACKEND": "gloo"})
     assert j["n_gpus"] == 2 and j["scaling"] == "strong" and j["control_plane"] == "gloo" and j["control_plane_ranks"] == 2
     assert j["config"]["global_batch"] == 3000 and j["config"]["rows_per_gpu"] == 1500
@@ -59,3 +68,27 @@ def test_two_ranks_without_launcher_strong_split_over_gloo():
     # a straggler would show in the per-rank lists; the N = 1 blocks stay off an N > 1 line
     assert j["per_rank"]["rows"] == [1500, 1500] and len(j["per_rank"]["kernel_ms"]) == 2 and min(j["per_rank"]["kernel_ms"]) > 0
     assert j["latency"] is None and j["strong_scaling_n1_point"] is None and j["spinup_launches"] >= 40          # at least 40 launches and 0.15 s of them (bench.py: SPINUP, SPINUP_SECONDS)
+
+
+def dumped_words(d, suffix=""):
+    hi, lo = np.load(os.path.join(d, f"c_hi{suffix}.npy")), np.load(os.path.join(d, f"c_lo{suffix}.npy"))
+    assert hi.dtype == lo.dtype == np.float64 and hi.shape == lo.shape
+    return hi.astype(np.uint64) << np.uint64(32) | lo.astype(np.uint64)
+
+
+def test_plain_line_and_dumped_outputs(tmp_path, oracle):
+    """A plain run (no --full): the contract fields, exactly K timed steps, none of the --full blocks; --dump-outputs writes the
+    sampled rows of the last step's products, and they are the negacyclic products of global rows make_poly(2r+1) x make_poly(2r+2)."""
+    j = run_bench("--steps", "4", "--warmup", "1", "--rows", "2048", "--dump-outputs", str(tmp_path))
+    assert j["steps"] == 4 and j["warmup"] == 1 and j["full"] is False and j["ms_per_step"] > 0 and j["value"] > 0
+    assert j["unit"] == "poly-mults/s" and j["higher_is_better"] is True and j["dtype"] == "u64"
+    assert abs(j["value"] - 2048 / (j["ms_per_step"] * 1e-3)) < 1e-3 * j["value"]
+    assert not {"parity", "roofline", "cpu_baseline", "latency", "strong_scaling_n1_point"} & set(j)
+    assert sorted(os.listdir(tmp_path)) == ["c_hi.npy", "c_lo.npy"]
+    c = dumped_words(tmp_path)
+    rows = bench.dump_rows(2048, 1)
+    n, q, psi = PARAMS["P4096_60"]
+    assert c.shape == (len(rows), n) == (512, 4096)
+    for i in (0, 100, len(rows) - 1):
+        r = int(rows[i])
+        assert np.array_equal(c[i], oracle.poly_mult(oracle.make_poly(2 * r + 1, n, q), oracle.make_poly(2 * r + 2, n, q), q, psi)), r
