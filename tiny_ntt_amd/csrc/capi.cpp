@@ -108,6 +108,7 @@ static tn_status plan_new(tn_plan** out, PlanKind kind, uint32_t n, uint64_t q, 
   p->n = n; p->logn = logn; p->q = q; p->psi = kind == PLAN_OMEGA ? 0 : t.psi; p->omega = t.omega;
   p->device = device; p->flags = flags; p->elem_bytes = elem_bytes;
   p->k = t.k; p->lazy = t.lazy; p->cg_lazy = t.cg_lazy; p->cg_sched = t.cg_sched;
+  p->bc_ok = kind == PLAN_PSI && t.bc_ok;
   p->canonical_inputs = kind == PLAN_PSI && (flags & TN_PLAN_CANONICAL_INPUTS) && t.cin_ok;
   p->omega_only = kind == PLAN_OMEGA; p->general = kind != PLAN_PSI;       // (no reversal trick without omega^(n/2) == -1)
   if (elem_bytes == 8) p->ar64 = h_make_arith<u64>(t); else p->ar32 = h_make_arith<u32>(t);
@@ -119,7 +120,8 @@ static tn_status plan_new(tn_plan** out, PlanKind kind, uint32_t n, uint64_t q, 
   struct Up { const std::vector<u64>* v; void** d; };
   const Up ups[] = {{&t.psi_brv, &p->d_psi_brv}, {&t.psi_inv_brv, &p->d_psi_inv_brv}, {&t.omega_pow, &p->d_omega_pow},
                     {&t.omega_inv_pow, &p->d_omega_inv_pow}, {&t.psi_pow, &p->d_psi_pow}, {&t.psi_inv_ninv, &p->d_psi_inv_ninv},
-                    {&t.psi_inv_pow, &p->d_psi_inv_pow}, {&t.cyc_brv, &p->d_cyc_brv}, {&t.cyc_inv_brv, &p->d_cyc_inv_brv}};
+                    {&t.psi_inv_pow, &p->d_psi_inv_pow}, {&t.cyc_brv, &p->d_cyc_brv}, {&t.cyc_inv_brv, &p->d_cyc_inv_brv},
+                    {&t.psi_bc, &p->d_psi_bc}, {&t.cyc_bc, &p->d_cyc_bc}};
   hipError_t e = hipSuccess;
   for (const Up& u : ups)
     if (e == hipSuccess && !u.v->empty()) e = upload_tw(*u.v, t, true, u.d);      // (record format: h_make_fused_tw — Shoup unless lazy 64-bit)
@@ -148,7 +150,7 @@ extern "C" tn_status tn_plan_create_general(tn_plan** out, uint32_t n, uint64_t 
 extern "C" tn_status tn_plan_destroy(tn_plan* p) {
   if (!p) return TN_OK;
   DeviceGuard guard(p->device);
-  void* tabs[] = {p->d_psi_brv, p->d_psi_inv_brv, p->d_omega_pow, p->d_omega_inv_pow, p->d_psi_pow, p->d_psi_inv_ninv, p->d_psi_inv_pow, p->d_cyc_brv, p->d_cyc_inv_brv, p->d_scratch, p->d_sched};
+  void* tabs[] = {p->d_psi_brv, p->d_psi_inv_brv, p->d_omega_pow, p->d_omega_inv_pow, p->d_psi_pow, p->d_psi_inv_ninv, p->d_psi_inv_pow, p->d_cyc_brv, p->d_cyc_inv_brv, p->d_psi_bc, p->d_cyc_bc, p->d_scratch, p->d_sched};
   for (void* t : tabs) if (t) (void)hipFree(t);
   for (unsigned i = 0; i < tn_plan::SCHED_SLOTS; ++i) if (p->sched_ev[i]) (void)hipEventDestroy(p->sched_ev[i]);
   if (p->ev0) (void)hipEventDestroy(p->ev0);

@@ -63,6 +63,10 @@ template <typename E> struct Arith {
   // (split for lazy 64-bit plans, Shoup otherwise):
   typename TwOf<E>::type fninv;      // n^-1
   typename TwOf<E>::type fninv_w1;   // n^-1 * psi_inv_brv[1]  (odd half)
+  // ... of the product kernel with the base case (incomplete transform: the inverse runs log2(n) - 1 stages and the base case
+  // leaves a factor 2 less than the pointwise product + first inverse stage it replaces): (n/2)^-1 and (n/2)^-1 psi_inv_brv[1]
+  typename TwOf<E>::type bninv;
+  typename TwOf<E>::type bninv_w1;
 };
 
 template <typename E, int LOGN_, int LPT_> struct FusedCfg {
@@ -291,13 +295,20 @@ template <typename P, int LOGN> struct Sched {
 //                         folded first; outputs u + v, tmax(u + Kv q)
 // The decisions are compile-time guesses in coarse units; h_split_sched_ok() (plan_tables.h) replays them with
 // exact 128-bit bounds for the plan's (k, c), and a plan whose modulus fails that replay is not lazy.
-template <typename Cfg, bool CIN = false> struct SplitSched {
+//   Base case (BC: the product kernel's incomplete transform, basecase() below): the forward stops one stage early
+//   (FEND = LOGN - 1) and the inverse starts one stage late (g = 1).  Operand b is converted to records (any word);
+//   a's registers are multiplicands: a register above BC_AMAX is folded first so that the products with b's records
+//   (whose x part is not reduced: split_rec) keep H < 2^64.  Outputs: c0 < tmax(ba0) + tmax(tmax(ba1)),
+//   c1 < tmax(ba0) + tmax(ba1).
+template <typename Cfg, bool CIN = false, bool BC = false> struct SplitSched {
   static constexpr int LOGN = Cfg::LOGN, R = Cfg::R;
+  static constexpr int FEND = BC ? LOGN - 1 : LOGN;
   static constexpr long U = 4096, CAP = 16 * U;
   static constexpr long FOLDED = U + 1;            // fold(): < 2^k + 2^(64-k) c
   static constexpr long PW_OUT = 2 * U;            // mulmod_solinas_lazy: < 2q
   static constexpr long PW_IN = 14 * (U - 1);      // ... for an unfolded operand below 14 q
   static constexpr long tmax(long bv) { return 4 * U + (bv + 7) / 8 + 2; }
+  static constexpr long BC_AMAX = CAP - 8;         // base case: largest multiplicand bound of a data record (h_bc_sched_ok)
   static constexpr int kq(long b) { return (int)((b + U - 2) / (U - 1)); }      // smallest K with K q >= b  (q >= (U-1) units)
   // The multiples K q live in SGPR pairs; only a few distinct ones are used so that they stay resident across the
   // persistent row loop: 6q or 7q in the forward butterflies, multiples of 4q in the inverse ones (one more fold per
@@ -311,6 +322,7 @@ template <typename Cfg, bool CIN = false> struct SplitSched {
     unsigned char fk[LOGN][R] = {};    // forward stage s: K of the butterfly whose u is register r
     long fout = 0;                     // bound of every forward output
     bool pw_fold_b = false;            // pointwise: the second operand must be folded too
+    bool bcfold[R] = {};               // base case: fold register r of a first
     bool ifold[LOGN][R] = {};          // inverse stage g (execution order): fold register r first
     unsigned char ik[LOGN][R] = {};    // inverse stage g: Kv of the butterfly whose u is register r
   };
@@ -320,7 +332,7 @@ template <typename Cfg, bool CIN = false> struct SplitSched {
     // forward: load_reduce() folds the registers that enter stage 0 as "u" (the low half), the rest are raw words;
     // promised-canonical inputs: every register is below q
     for (int r = 0; r < R; ++r) b[r] = CIN ? U : (r < R / 2 ? FOLDED : CAP);
-    for (int s = 0; s < LOGN; ++s) {
+    for (int s = 0; s < FEND; ++s) {
       if (s > 0 && phase_of(s) != phase_of(s - 1)) {
         long m = 0;
         for (int r = 0; r < R; ++r) m = b[r] > m ? b[r] : m;
@@ -342,8 +354,16 @@ template <typename Cfg, bool CIN = false> struct SplitSched {
     for (int r = 0; r < R; ++r) d.fout = b[r] > d.fout ? b[r] : d.fout;
     d.pw_fold_b = d.fout > PW_IN;
     // inverse, execution order g (g = 0 undoes forward stage LOGN-1)
-    for (int r = 0; r < R; ++r) b[r] = PW_OUT;
-    for (int g = 0; g < LOGN; ++g) {
+    // (base case: from the forward outputs of the register pair, a's and b's alike)
+    for (int r = 0; r < R; r += 2) {
+      if (!BC) { b[r] = b[r + 1] = PW_OUT; continue; }
+      long a0 = b[r], a1 = b[r + 1];
+      if (a0 > BC_AMAX) { d.bcfold[r] = true; a0 = FOLDED; }
+      if (a1 > BC_AMAX) { d.bcfold[r + 1] = true; a1 = FOLDED; }
+      b[r] = tmax(a0) + tmax(tmax(a1));
+      b[r + 1] = tmax(a0) + tmax(a1);
+    }
+    for (int g = BC ? 1 : 0; g < LOGN; ++g) {
       const int s = LOGN - 1 - g;
       if (g > 0 && phase_of(s) != phase_of(s + 1)) {
         long m = 0;
@@ -372,7 +392,7 @@ template <typename Cfg, bool CIN = false> struct SplitSched {
 };
 
 // What the phase loops ask the schedule of their policy.
-template <typename Pol, typename Cfg> struct SchedOf {
+template <typename Pol, typename Cfg, bool BC = false> struct SchedOf {
   typedef Sched<Pol, Cfg::LOGN> S;
   static constexpr bool fwd_fold(int s, int r) { return S::fwd_fold(s) && !(r & (1 << SplitSched<Cfg>::bpos_of(s))); }
   static constexpr int fwd_k(int, int) { return Pol::TMUL; }
@@ -381,14 +401,15 @@ template <typename Pol, typename Cfg> struct SchedOf {
   static constexpr bool pw_fold_b() { return false; }
   static constexpr bool pw_ok() { return !Pol::lazy || S::fwd_out() <= Pol::LIMIT - 2; }
 };
-template <typename Cfg, bool CIN> struct SchedOf<Policy<u64, true, CIN>, Cfg> {
-  typedef SplitSched<Cfg, CIN> S;
+template <typename Cfg, bool CIN, bool BC> struct SchedOf<Policy<u64, true, CIN>, Cfg, BC> {
+  typedef SplitSched<Cfg, CIN, BC> S;
   static constexpr bool fwd_fold(int s, int r) { return S::D.ffold[s][r]; }
   static constexpr int fwd_k(int s, int r) { return S::D.fk[s][r]; }
   static constexpr bool inv_fold(int g, int r) { return S::D.ifold[g][r]; }
   static constexpr int inv_k(int g, int r) { return S::D.ik[g][r]; }
   static constexpr bool pw_fold_b() { return S::D.pw_fold_b; }
   static constexpr bool pw_ok() { return true; }
+  static constexpr bool bc_fold(int r) { return S::D.bcfold[r]; }
 };
 
 // The three places a phase can take its twiddles from (see FusedCfg::tw_src).
@@ -475,12 +496,14 @@ TN_HD void tw_prefetch(typename TwOf<E>::type (&pre)[Cfg::NPRE], u32 tau, const 
 
 // ---------------------------------------------------------------------------
 // One forward phase on a thread's registers.
-template <typename E, typename Cfg, typename Pol, int PH>
+// BC: the product kernel's incomplete transform (the last stage, LOGN - 1, is left to basecase()).
+template <typename E, typename Cfg, typename Pol, int PH, bool BC = false>
 TN_HD void fwd_phase(E (&x)[Cfg::R], u32 tau, const TwRefs<E>& tw, const Arith<E>& ar) {
-  typedef SchedOf<Pol, Cfg> SO;
+  typedef SchedOf<Pol, Cfg, BC> SO;
   typedef typename TwOf<E>::type Tw;
   const u32 thi = Cfg::thi(PH, tau);
-  static_for<Cfg::stage_begin(PH), Cfg::stage_end(PH)>([&](auto s_) {
+  constexpr int SEND = BC && Cfg::stage_end(PH) == Cfg::LOGN ? Cfg::LOGN - 1 : Cfg::stage_end(PH);
+  static_for<Cfg::stage_begin(PH), SEND>([&](auto s_) {
     constexpr int s = decltype(s_)::value;
     constexpr int bpos = (Cfg::LOGN - 1 - s) - Cfg::pos(PH);
     // only the "u" side of a butterfly can need its bound back: the "v" side goes through the twiddle
@@ -500,13 +523,15 @@ TN_HD void fwd_phase(E (&x)[Cfg::R], u32 tau, const TwRefs<E>& tw, const Arith<E
 }
 
 // One inverse phase (stages of phase PH in reverse order).
-template <typename E, typename Cfg, typename Pol, int PH>
+// BC: starts one stage late (the base case has done the work of the first one).
+template <typename E, typename Cfg, typename Pol, int PH, bool BC = false>
 TN_HD void inv_phase(E (&x)[Cfg::R], u32 tau, const TwRefs<E>& tw, const Arith<E>& ar) {
-  typedef SchedOf<Pol, Cfg> SO;
+  typedef SchedOf<Pol, Cfg, BC> SO;
   typedef typename TwOf<E>::type Tw;
   const u32 thi = Cfg::thi(PH, tau);
-  static_for<0, Cfg::stage_end(PH) - Cfg::stage_begin(PH)>([&](auto i_) {
-    constexpr int s = Cfg::stage_end(PH) - 1 - decltype(i_)::value;   // forward stage number being undone
+  constexpr int SEND = BC && Cfg::stage_end(PH) == Cfg::LOGN ? Cfg::LOGN - 1 : Cfg::stage_end(PH);
+  static_for<0, SEND - Cfg::stage_begin(PH)>([&](auto i_) {
+    constexpr int s = SEND - 1 - decltype(i_)::value;                  // forward stage number being undone
     constexpr int g = Cfg::LOGN - 1 - s;                               // execution order of the inverse
     constexpr int bpos = (Cfg::LOGN - 1 - s) - Cfg::pos(PH);
     static_for<0, Cfg::R>([&](auto r_) {
@@ -571,6 +596,38 @@ TN_HD void pointwise(E (&xa)[Cfg::R], const E (&xb)[Cfg::R], const Arith<E>& ar)
       xa[r] = mulmod_barrett(xa[r], xb[r], ar.q, ar.mu, ar.k);
     if (r & 1) sched_fence();          // two products in flight at a time: bounds the live temporaries
   }
+}
+
+// Base case of the incomplete transform (lazy 64-bit lanes; replaces the last forward stage of both operands, the pointwise
+// product and the first inverse stage).  After forward stages 0 .. LOGN-2, registers (r, r+1) of the last phase hold the
+// residues of a and b mod y^2 - zeta, zeta = w^2 (w: the skipped stage's twiddle; the zeta table holds its split record).
+// Their product mod y^2 - zeta is
+//   c0 = a0 b0 + zeta a1 b1,  c1 = a0 b1 + a1 b0,
+// which is 1/2 of what forward stage LOGN-1, the pointwise product and inverse stage 0 produce (that factor 2 is taken out
+// of the last inverse stage: Arith::bninv).  b is turned into records once (split_rec) and each record is used twice;
+// zeta a1 is a twiddle product that rides as the addend of c0's second product.  30 + 2 x 2 multiply-adds per pair.
+TN_HD void basecase_pair(u64& a0, u64& a1, u64 b0, u64 b1, Tw64 zeta, const Arith<u64>& ar) {
+  const Tw64 B0 = split_rec(b0, ar.k, ar.fold_c, ar.q), B1 = split_rec(b1, ar.k, ar.fold_c, ar.q);
+  // (opaque: the first product of each output is the addend of the second; seen through, LLVM re-associates the two chains
+  //  into separate sums joined by 64-bit adds and zero-extending moves)
+  const u64 t = opaque64(mul_sp(a1, zeta, ar.sk));
+  const u64 c0 = mul_sp_acc(opaque64(mul_sp(a0, B0, ar.sk)), t, B1, ar.sk);
+  const u64 c1 = mul_sp_acc(opaque64(mul_sp(a0, B1, ar.sk)), a1, B0, ar.sk);
+  a0 = c0;
+  a1 = c1;
+}
+// zeta: the calling thread's records of the last stage, in the order of its register pairs.
+template <typename Cfg, typename Pol>
+TN_HD void basecase(u64 (&xa)[Cfg::R], const u64 (&xb)[Cfg::R], const Tw64* zeta, const Arith<u64>& ar) {
+  typedef SchedOf<Pol, Cfg, true> SO;
+  static_assert(Pol::split && Cfg::pos(Cfg::PHASES - 1) == 0, "base case: split policy, pairs in neighbouring registers");
+  static_for<0, Cfg::R / 2>([&](auto i_) {
+    constexpr int r = 2 * decltype(i_)::value;
+    if constexpr (SO::bc_fold(r)) xa[r] = fold(xa[r], ar.k, ar.fold_c);
+    if constexpr (SO::bc_fold(r + 1)) xa[r + 1] = fold(xa[r + 1], ar.k, ar.fold_c);
+    basecase_pair(xa[r], xa[r + 1], xb[r], xb[r + 1], zeta[r / 2], ar);
+    sched_fence();                     // one pair in flight at a time: bounds the live temporaries
+  });
 }
 
 }  // namespace tn

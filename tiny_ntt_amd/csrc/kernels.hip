@@ -181,7 +181,8 @@ __device__ __forceinline__ const Arith<E>& kernarg_arith(u32 zero) {
 // Forward transform, phases [P0, P1).  The thread-private twiddles of the last phase live in tw.pre[]; with `fetch_pre` they
 // are requested from L2 just before the transpose that precedes that phase, so their latency hides behind it.
 // KARG: take the arithmetic constants and the scalar twiddles of each phase through a fresh opaque zero (see kernarg_arith).
-template <typename E, typename Cfg, typename Pol, int P0, int P1, bool KARG = false, int PRE_END = Cfg::LOGN>
+// BC: the base-case product's incomplete transform (fwd_phase).
+template <typename E, typename Cfg, typename Pol, int P0, int P1, bool KARG = false, int PRE_END = Cfg::LOGN, bool BC = false>
 __device__ __forceinline__ void forward_range(E (&x)[Cfg::R], u32 tau, const TwRefs<E>& tw_in, const Arith<E>& ar_in, E* lds, bool fetch_pre,
                                               u32 tau_g) {      // tau_g: the thread index again, for global addressing (opaque_copy)
   typename TwOf<E>::type vec[Cfg::R];        // twiddles of a vector-loaded phase (n = 8192), requested one transpose ahead
@@ -193,7 +194,7 @@ __device__ __forceinline__ void forward_range(E (&x)[Cfg::R], u32 tau, const TwR
     if constexpr (KARG) tw.zero = opaque_zero();
     if constexpr (TN_VEC_PREFETCH && Cfg::tw_src(p) == Cfg::TW_VEC && FULL && p > P0) tw.mid = vec;
     const Arith<E>& ar = KARG ? kernarg_arith<E>(tw.zero) : ar_in;
-    fwd_phase<E, Cfg, Pol, p>(x, tau, tw, ar);
+    fwd_phase<E, Cfg, Pol, p, BC>(x, tau, tw, ar);
     TN_MARK("fwd_other");
     if constexpr (p == Cfg::PHASES - 2) {
       if (fetch_pre) {
@@ -225,7 +226,7 @@ __device__ __forceinline__ void forward_all(E (&x)[Cfg::R], u32 tau, const typen
 // twiddles come from L2 through vector loads) has been computed: vector-memory operations
 // complete in order, so the long-latency HBM prefetch of the next row must be issued AFTER
 // those twiddle loads have been consumed, or every wave would wait for HBM at the top of the inverse.
-template <typename E, typename Cfg, typename Pol, bool KARG = false, typename F>
+template <typename E, typename Cfg, typename Pol, bool KARG = false, bool BC = false, typename F>
 __device__ __forceinline__ void inverse_all(E (&x)[Cfg::R], u32 tau, const TwRefs<E>& tw_in, const Arith<E>& ar_in, E* lds,
                                             F&& after_first) {
   typename TwOf<E>::type vec[Cfg::R];        // twiddles of a vector-loaded phase (n = 8192), requested one transpose ahead
@@ -237,7 +238,7 @@ __device__ __forceinline__ void inverse_all(E (&x)[Cfg::R], u32 tau, const TwRef
     if constexpr (KARG) tw.zero = opaque_zero();
     if constexpr (TN_VEC_PREFETCH && Cfg::tw_src(p) == Cfg::TW_VEC && FULL && p < Cfg::PHASES - 1) tw.mid = vec;
     const Arith<E>& ar = KARG ? kernarg_arith<E>(tw.zero) : ar_in;
-    inv_phase<E, Cfg, Pol, p>(x, tau, tw, ar);
+    inv_phase<E, Cfg, Pol, p, BC>(x, tau, tw, ar);
     TN_MARK("inv_other");
     // (the next phase's vector-loaded twiddles are requested BEFORE the next row's HBM prefetch: vector-memory operations return
     //  in order, and behind the prefetch the phase would wait for HBM: n = 8192 cg_intt, profiles/r3_n8192_ab.txt)
@@ -304,7 +305,10 @@ constexpr int polymul_waves() {
   return LPT >= 4 ? 2 : (sizeof(E) == 8 && LOGN == 12 && LAZY) ? TN_POLYMUL60_WAVES : TN_FUSED_MIN_WAVES;
 }
 
-template <typename E, int LOGN, int LPT, bool LAZY, bool CIN = false>
+// BC (n = 4096 / 64-bit lazy only): both forward transforms stop one stage early, basecase() replaces the last stage, the
+// pointwise product and the first inverse stage (fused_core.h); tab_fwd is then the plan's psi_bc / cyc_bc table, whose last
+// level holds the base case's zeta records, and ar.fninv / fninv_w1 carry (n/2)^-1 (launch_fused_t).
+template <typename E, int LOGN, int LPT, bool LAZY, bool CIN = false, bool BC = false>
 __global__ void __launch_bounds__((1 << (LOGN - LPT)), (polymul_waves<E, LOGN, LPT, LAZY>()))
 polymul_fused_kernel(const Arith<E> ar, const typename TwOf<E>::type* __restrict__ tab_fwd,
                      const typename TwOf<E>::type* __restrict__ tab_inv, const E* __restrict__ a, const E* __restrict__ b,
@@ -395,21 +399,22 @@ polymul_fused_kernel(const Arith<E> ar, const typename TwOf<E>::type* __restrict
                             Cfg::stage_end(PM) - Cfg::stage_begin(PM) == Cfg::LPT;
     const TwRefs<E> twf = {tab_fwd, lds_fwd, prf, nullptr, zero};
     // A^ stays in registers while b is transformed
-    if constexpr (SHARE2) forward_range<E, Cfg, Pol, 0, PM, KARG>(xa, tau, twf, ar, lds, false, tl);
+    static_assert(!BC || SHARE2, "base case: built for the shared-twiddle schedule only");
+    if constexpr (SHARE2) forward_range<E, Cfg, Pol, 0, PM, KARG, Cfg::LOGN, BC>(xa, tau, twf, ar, lds, false, tl);
     else if constexpr (SHARE) forward_range<E, Cfg, Pol, 0, Cfg::PHASES - 1, KARG>(xa, tau, twf, ar, lds, false, tl);
     else forward_all<E, Cfg, Pol>(xa, tau, tab_fwd, lds_fwd, ar, lds, zero);
     __syncthreads();
     const u32 next = wave_uniform(*lds_next);
     load_reduce<E, Cfg, Pol>(xb, ar);
     if constexpr (SHARE2) {
-      forward_range<E, Cfg, Pol, 0, PM, KARG>(xb, tau, twf, ar, lds, false, tl);
+      forward_range<E, Cfg, Pol, 0, PM, KARG, Cfg::LOGN, BC>(xb, tau, twf, ar, lds, false, tl);
       Tw mid[Cfg::R];
       tw_fetch_mid<E, Cfg, PM>(mid, tau, lds_fwd);
       const TwRefs<E> twm = {tab_fwd, lds_fwd, prf, mid, zero};
-      forward_range<E, Cfg, Pol, PM, PM + 1, KARG>(xa, tau, twm, ar, lds, false, tl);
-      forward_range<E, Cfg, Pol, PM, PM + 1, KARG, PRE_END>(xb, tau, twm, ar, lds, true, tl);
-      forward_range<E, Cfg, Pol, PM + 1, Cfg::PHASES, KARG>(xb, tau, twf, ar, lds, false, tl);
-      forward_range<E, Cfg, Pol, PM + 1, Cfg::PHASES, KARG>(xa, tau, twf, ar, lds, false, tl);
+      forward_range<E, Cfg, Pol, PM, PM + 1, KARG, Cfg::LOGN, BC>(xa, tau, twm, ar, lds, false, tl);
+      forward_range<E, Cfg, Pol, PM, PM + 1, KARG, PRE_END, BC>(xb, tau, twm, ar, lds, true, tl);
+      forward_range<E, Cfg, Pol, PM + 1, Cfg::PHASES, KARG, Cfg::LOGN, BC>(xb, tau, twf, ar, lds, false, tl);
+      forward_range<E, Cfg, Pol, PM + 1, Cfg::PHASES, KARG, Cfg::LOGN, BC>(xa, tau, twf, ar, lds, false, tl);
     } else if constexpr (SHARE) {
       forward_range<E, Cfg, Pol, 0, Cfg::PHASES - 1, KARG, PRE_END>(xb, tau, twf, ar, lds, true, tl);
       forward_range<E, Cfg, Pol, Cfg::PHASES - 1, Cfg::PHASES, KARG>(xb, tau, twf, ar, lds, false, tl);
@@ -418,13 +423,21 @@ polymul_fused_kernel(const Arith<E> ar, const typename TwOf<E>::type* __restrict
       forward_all<E, Cfg, Pol>(xb, tau, tab_fwd, lds_fwd, ar, lds, zero);
     }
     // the inverse starts with the thread-private phase: request its twiddles before the product
+    // (base case: the inverse's private phase has one stage less, so 3 of the 7 records; the zeta records came with prf)
     Tw pre[Cfg::NPRE];
-    tw_prefetch<E, Cfg>(pre, tl, tab_inv);
-    TN_MARK("pointwise");
-    pointwise<E, Cfg, Pol>(xa, xb, ar);
+    if constexpr (BC) {
+      TN_MARK("basecase");
+      basecase<Cfg, Pol>(xa, xb, prf + Cfg::pre_off(Cfg::LOGN - 1), ar);
+      sched_fence();
+      tw_prefetch_stages<E, Cfg, Cfg::stage_begin(Cfg::PHASES - 1), Cfg::LOGN - 1>(pre, tl, tab_inv);
+    } else {
+      tw_prefetch<E, Cfg>(pre, tl, tab_inv);
+      TN_MARK("pointwise");
+      pointwise<E, Cfg, Pol>(xa, xb, ar);
+    }
     TN_MARK("after_pointwise");
     const TwRefs<E> twi = {tab_inv, lds_inv, pre, nullptr, zero};
-    inverse_all<E, Cfg, Pol, KARG>(xa, tau, twi, ar, lds, [&]() {
+    inverse_all<E, Cfg, Pol, KARG, BC>(xa, tau, twi, ar, lds, [&]() {
       // next row's first operand -> the registers that held b.  Unconditional (after the last row this row's a is read
       // again and dropped): a branch here costs a register copy of all R values on the path that skips it.
       const u32 nrow = next < batch ? next : row;
@@ -633,8 +646,13 @@ static hipError_t launch_fused_t(const tn_plan* p, const void* a, const void* b,
   // box (same 1,963 vector instructions per wave and row, 36 instead of 8 bytes of scratch: profiles/r3_headline_ledger.txt), so the
   // shipped library accepts the promise and runs the any-word kernel.
   constexpr bool HAS_CIN = TN_FUSED_CIN && sizeof(E) == 8 && LOGN == 12 && LAZY;
+  // base case (fused_core.h basecase()): the n = 4096 / 64-bit lazy kernel, for plans whose (k, c) passes h_bc_sched_ok();
+  // measured in profiles/r4_basecase_ab.txt.  Other shapes keep the last stage and the pointwise product.
+  constexpr bool HAS_BC = sizeof(E) == 8 && LOGN == 12 && LPT == 3 && LAZY;
+  bool use_bc = false;
   auto kern = polymul_fused_kernel<E, LOGN, LPT, LAZY>;
   if constexpr (HAS_CIN) { if (p->canonical_inputs && !cyclic) kern = polymul_fused_kernel<E, LOGN, LPT, LAZY, true>; }
+  if constexpr (HAS_BC) { if (p->bc_ok && !(HAS_CIN && p->canonical_inputs && !cyclic)) { kern = polymul_fused_kernel<E, LOGN, LPT, LAZY, false, true>; use_bc = true; } }
   if (lds_bytes > 48 * 1024) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
     if (e != hipSuccess) return e;
@@ -652,12 +670,14 @@ static hipError_t launch_fused_t(const tn_plan* p, const void* a, const void* b,
   // cyclic = product in Z_q[x]/(x^n - 1) (python_poly_mult, test_ntt_poly_mult.py:38-43): same kernel, twiddle
   // tables of the x^n - 1 factorisation tree (HostTables::cyc_brv), whose inverse table has entry 1 equal to 1
   Arith<E> ar = pv.ar;
+  if (use_bc) { ar.fninv = ar.bninv; ar.fninv_w1 = ar.bninv_w1; }        // the inverse runs log2(n) - 1 stages: (n/2)^-1
   if (cyclic) ar.fninv_w1 = ar.fninv;
+  const typename TwOf<E>::type* tab_fwd = use_bc ? (cyclic ? pv.cyc_bc : pv.psi_bc) : (cyclic ? pv.cyc_brv : pv.psi_brv);
   // one counter pair per launch in flight (ring; each pair is re-armed by the kernel that used it)
   SchedSlot slot;
   if (rp.dynamic) slot = sched_acquire(p, s);
   u32* sched = slot.ptr;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(Cfg::THREADS), lds_bytes, s, ar, cyclic ? pv.cyc_brv : pv.psi_brv,
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(Cfg::THREADS), lds_bytes, s, ar, tab_fwd,
                      cyclic ? pv.cyc_inv_brv : pv.psi_inv_brv, (const E*)a, (const E*)b, (E*)c, (u32)batch, sched, chunk);
   const hipError_t le = hipGetLastError();
   sched_release(p, slot, s, le == hipSuccess);

@@ -252,6 +252,26 @@ TN_HD u64 fold(u64 x, int k, u32 c) {
   return (x & lowmask) + (u64)top * c;
 }
 
+// Split record of a DATA value (the base case of the incomplete transform, fused_core.h): any 64-bit b -> the record of
+// w = (b mod q) in [0, q) with x = w 2^32 (mod q), so that mul_sp_acc(u, a, split_rec(b)) == u + a b (mod q).
+//   w = fold(b) with one conditional subtraction (fold() lands below 2q);
+//   x = (w >> s) c + (w mod 2^s) 2^32, s = k - 32 (2^k == c): NOT reduced, x < 2^32 c + 2^k, so xhi may exceed 2^31 by
+//       2^32 c >> p; the product then still fits (H < 2^64) for every multiplicand below ~2^64 - 2^(p+33) c / 2^31, which the
+//       base case's bound schedule guarantees (SplitSched, replayed exactly by h_bc_sched_ok() in plan_tables.h).
+// Two multiply-adds (fold, x) and no division.
+TN_HD Tw64 split_rec(u64 b, int k, u32 c, u64 q) {
+  const u64 w = csub(fold(b, k, c), q);
+  const int s = k - 32, p = k - 31;
+  const u32 mp = (1u << p) - 1u;
+  const u64 xl = (u64)(u32)(w >> s) * c;                                  // (w >> s) c < 2^32 c
+  const u32 xh = opaque32((u32)(xl >> 32) + ((u32)w & ((1u << s) - 1u)));   // + (w mod 2^s) on the high dword: no carry in
+  const u64 x = ((u64)xh << 32) | (u32)xl;
+  Tw64 t;
+  t.w = ((u64)(u32)(w >> p) << 32) | ((u32)w & mp);
+  t.wp = ((u64)(u32)(x >> p) << 32) | ((u32)x & mp);
+  return t;
+}
+
 // Two-operand product for q = 2^k - c with SMALL c (2^k == c mod q), used by the pointwise step of the lazy policy:
 // the 128-bit product is split at bit k and the high part folded back twice.  9 multiplies instead of the
 // 18 of a two-operand Barrett.  a: output of fold() (< 2^k + 2^(64-k) c); b: any value < 14q.  Result == a*b (mod q), < 2q.

@@ -15,6 +15,7 @@ struct tn_plan {
   tn::u32 flags = 0;
   int elem_bytes = 8;
   bool has_fused = false, lazy = false, cg_lazy = false, cg_sched = false;
+  bool bc_ok = false;              // the n = 4096 / 64-bit lazy product kernel runs the base case (HostTables::bc_ok)
   bool canonical_inputs = false;   // TN_PLAN_CANONICAL_INPUTS was given and the fused product kernel has a schedule for it (else the flag is ignored)
   bool omega_only = false;   // created by tn_plan_create_omega: no psi, only the constant-geometry transforms
   bool general = false;      // created by tn_plan_create_general: psi / q not validated, tables computed literally (cg_ntt.py:78-92 for ANY psi)
@@ -40,6 +41,8 @@ struct tn_plan {
   void* d_psi_inv_pow = nullptr;   // [n]   psi^-i
   void* d_cyc_brv = nullptr;       // [n]   merged twiddles of the cyclic transform (HostTables::cyc_brv): fused cg_ntt
   void* d_cyc_inv_brv = nullptr;   // [n]   their inverses: fused cg_intt
+  void* d_psi_bc = nullptr;        // [n]   psi_brv / cyc_brv with the last level squared: forward tables of the base-case product
+  void* d_cyc_bc = nullptr;        //       kernel (HostTables::psi_bc; bc_ok plans only)
   void* d_psi_inv_ninv = nullptr;  // [n]   psi^-i * n^-1  (untwist :92 fused with the n^-1 of :74-75)
   // Host-side mutable state (staging scratch, the host pipeline's streams / events, ev0 / ev1 of the timing helper): the
   // *_host entry points and tn_time_poly_mult_dev take this lock, so two host threads may share one plan; *_dev entry
@@ -77,6 +80,8 @@ template <typename E> struct PlanView {
   const Tw* psi_inv_pow;
   const Tw* cyc_brv;
   const Tw* cyc_inv_brv;
+  const Tw* psi_bc;
+  const Tw* cyc_bc;
 };
 
 template <typename E> inline const Arith<E>& plan_arith(const tn_plan* p);
@@ -93,6 +98,7 @@ template <typename E> inline PlanView<E> make_view(const tn_plan* p) {
   v.psi_pow = (const Tw*)p->d_psi_pow; v.psi_inv_ninv = (const Tw*)p->d_psi_inv_ninv;
   v.psi_inv_pow = (const Tw*)p->d_psi_inv_pow;
   v.cyc_brv = (const Tw*)p->d_cyc_brv; v.cyc_inv_brv = (const Tw*)p->d_cyc_inv_brv;
+  v.psi_bc = (const Tw*)p->d_psi_bc; v.cyc_bc = (const Tw*)p->d_cyc_bc;
   return v;
 }
 

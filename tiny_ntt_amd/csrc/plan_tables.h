@@ -14,13 +14,18 @@ struct HostTables {
   bool cg_lazy = false;      // lazy, 64-bit lanes, and the constant-geometry kernels may run lazy butterflies (h_cg_lazy_ok)
   bool cg_sched = false;     // ... with the static fold schedule (h_cg_sched_ok; even log2 n only)
   bool cin_ok = false;       // the fused product kernel's schedule for promised-canonical inputs is valid (h_split_sched_cin_ok)
+  bool bc_ok = false;        // the fused product kernel runs the base case instead of the last stage + pointwise product (h_bc_sched_ok)
   u32 fold_c = 0;
   u64 n_inv = 0, ninv_w1 = 0;
+  u64 n2_inv = 0, n2inv_w1 = 0;        // (n/2)^-1 and (n/2)^-1 psi_inv_brv[1]: last inverse stage after the base case
   std::vector<u64> psi_pow, psi_inv_pow, psi_inv_ninv, psi_brv, psi_inv_brv, omega_pow, omega_inv_pow;
   // merged twiddles of the CYCLIC transform (x^n - 1 factorisation tree): node m+i (m = 2^s nodes at level s) splits
   // x^(n/m) - zeta with sqrt(zeta) = psi^(brv(m+i) - n/(2m)); same butterflies, same bit-reversed output order as
   // the negacyclic table psi_brv, so cg_ntt / cg_intt run on the fused kernel without a pre- or post-twist
   std::vector<u64> cyc_brv, cyc_inv_brv;
+  // forward tables of the product kernel with the base case (bc_ok only): psi_brv / cyc_brv with the last level [n/2, n)
+  // replaced by the squares zeta = w^2 of its twiddles (the base case works mod y^2 - zeta; fused_core.h basecase())
+  std::vector<u64> psi_bc, cyc_bc;
 };
 
 inline u32 h_brv(u32 v, u32 bits) {
@@ -87,20 +92,29 @@ struct SplitExact {
     if (k < 32 || k > 60 || cf >= ((u64)1 << 32) || c >= ((u64)1 << 32)) ok = false;
   }
   // t' of mul_sp_acc for a value below bv (h_sp_tmax): exclusive bound; also checks that H fits 64 bits
-  u128 tmax(u128 bv) {
+  u128 tmax(u128 bv) { return tmax_rec(bv, (u128)((q - 1) >> p), (u128)((q - 1) >> p)); }
+  // ... for a record whose high parts are at most whi (w) and xhi (x); the low parts are below 2^p
+  u128 tmax_rec(u128 bv, u128 whi, u128 xhi) {
     const u128 m32 = (((u128)1) << 32) - 1;
     u128 a1 = (bv - 1) >> 32; if (a1 > m32) a1 = m32;
-    const u128 wlo = (((u128)1) << p) - 1, whi = (u128)((q - 1) >> p);
-    const u128 H = m32 * whi + a1 * whi;
-    if (H >= two64 || whi > m32) ok = false;
-    return m32 * wlo + a1 * wlo + (m32 << p) + (H >> 32) * cf + 1;
+    const u128 lo = (((u128)1) << p) - 1;
+    const u128 H = m32 * whi + a1 * xhi;
+    if (H >= two64 || whi > m32 || xhi > m32) ok = false;
+    return m32 * lo + a1 * lo + (m32 << p) + (H >> 32) * cf + 1;
+  }
+  // high parts of split_rec()'s records (modarith.h): w < q, x < 2^32 c + 2^k (not reduced); checks the x sum fits
+  u128 rec_whi() { return (u128)((q - 1) >> p); }
+  u128 rec_xhi() {
+    const u128 xmax = (((((u128)1) << 32) - 1) * c) + (((((u128)1) << (k - 32)) - 1) << 32);    // inclusive
+    if (xmax >= two64) ok = false;
+    return xmax >> p;
   }
   u128 folded(u128 b) { return (((u128)1) << k) + ((b - 1) >> k) * c; }           // fold() of a value below b
   void fits(u128 exclusive) { if (exclusive > two64) ok = false; }
 };
 
-template <typename Cfg, bool CIN = false> inline bool h_split_sched_replay(int k, u64 c) {
-  typedef SplitSched<Cfg, CIN> S;
+template <typename Cfg, bool CIN = false, bool BC = false> inline bool h_split_sched_replay(int k, u64 c) {
+  typedef SplitSched<Cfg, CIN, BC> S;
   typedef unsigned __int128 u128;
   SplitExact x(k, c);
   if (!x.ok) return false;
@@ -109,7 +123,7 @@ template <typename Cfg, bool CIN = false> inline bool h_split_sched_replay(int k
   u128 b[R];
   auto level = [&]() { u128 m = 0; for (int r = 0; r < R; ++r) m = b[r] > m ? b[r] : m; for (int r = 0; r < R; ++r) b[r] = m; };
   for (int r = 0; r < R; ++r) b[r] = CIN ? (u128)x.q : (r < R / 2 ? x.folded(x.two64) : x.two64);   // load_reduce(): low half folded, rest raw words (promised-canonical inputs: all below q)
-  for (int s = 0; s < LOGN; ++s) {
+  for (int s = 0; s < S::FEND; ++s) {
     if (s > 0 && S::phase_of(s) != S::phase_of(s - 1)) level();
     const int bit = 1 << S::bpos_of(s);
     for (int r = 0; r < R; ++r) {
@@ -122,13 +136,26 @@ template <typename Cfg, bool CIN = false> inline bool h_split_sched_replay(int k
       b[r] = bu + t - 1; b[r | bit] = bu + kq;
     }
   }
-  u128 fout = 0;
-  for (int r = 0; r < R; ++r) fout = b[r] > fout ? b[r] : fout;
+  u128 fout = 0, fo[R];
+  for (int r = 0; r < R; ++r) { fout = b[r] > fout ? b[r] : fout; fo[r] = b[r]; }
   if (x.folded(fout) > (u128)2 * x.q) x.ok = false;    // Policy::canon(): fold, one conditional subtraction
   if (!D.pw_fold_b && fout > (u128)14 * x.q) x.ok = false;       // mulmod_solinas_lazy's unfolded operand (h_pw_fast_ok)
   for (int r = 0; r < R; ++r) b[r] = (u128)2 * x.q;    // pointwise product: < 2q (h_pw_fast_ok); folded loads are below that too
-  if (x.folded(x.two64) > (u128)2 * x.q) x.ok = false;
-  for (int g = 0; g < LOGN; ++g) {
+  if (x.folded(x.two64) > (u128)2 * x.q) x.ok = false;  // (also: split_rec's one conditional subtraction lands below q)
+  if (BC) {
+    // base case (basecase_pair, fused_core.h) on the forward outputs fout[r] of both operands: b's records from split_rec;
+    // t = zeta a1 (twiddle record); c0 = a0 B0 + t B1, c1 = a0 B1 + a1 B0 with the second product riding on the first
+    const u128 whi = x.rec_whi(), xhi = x.rec_xhi();
+    for (int r = 0; r < R; r += 2) {
+      const u128 a0 = D.bcfold[r] ? x.folded(fo[r]) : fo[r], a1 = D.bcfold[r + 1] ? x.folded(fo[r + 1]) : fo[r + 1];
+      const u128 t = x.tmax(a1);
+      const u128 p0 = x.tmax_rec(a0, whi, xhi), p1 = x.tmax_rec(t, whi, xhi), p2 = x.tmax_rec(a1, whi, xhi);
+      x.fits(p0 + p1 - 1); x.fits(p0 + p2 - 1);
+      b[r] = p0 + p1 - 1;
+      b[r + 1] = p0 + p2 - 1;
+    }
+  }
+  for (int g = BC ? 1 : 0; g < LOGN; ++g) {
     const int s = LOGN - 1 - g;
     if (g > 0 && S::phase_of(s) != S::phase_of(s + 1)) level();
     const int bit = 1 << S::bpos_of(s);
@@ -228,6 +255,12 @@ inline bool h_split_sched_cin_ok(u32 logn, int k, u64 c) {
   return logn == 12 && h_split_sched_replay<FusedCfg<u64, 12, fused_lpt(12)>, true>(k, c);
 }
 
+// ... and of the product kernel with the base case (built for n = 4096 only: kernels.hip, launch_fused_t).  A (k, c) that
+// fails it keeps the kernel with the last stage and the pointwise product.
+inline bool h_bc_sched_ok(u32 logn, int k, u64 c) {
+  return logn == 12 && h_split_sched_replay<FusedCfg<u64, 12, fused_lpt(12)>, false, true>(k, c);
+}
+
 // Is the split-constant lazy policy valid for this (n, k, c)?  (false too when no fused kernel is built for n)
 inline bool h_split_sched_ok(u32 logn, int k, u64 c) {
   switch (logn) {
@@ -257,6 +290,7 @@ inline HostTables h_build_tables(u32 n, u64 q, u64 psi, bool allow_lazy) {
   t.cg_lazy = t.lazy && t.elem_bytes == 8 && h_cg_lazy_ok(t.k, t.fold_c);
   t.cg_sched = t.cg_lazy && (logn & 1) == 0 && h_cg_sched_ok(t.k, t.fold_c);
   t.cin_ok = t.lazy && t.elem_bytes == 8 && h_split_sched_cin_ok(logn, t.k, t.fold_c);
+  t.bc_ok = t.lazy && t.elem_bytes == 8 && h_bc_sched_ok(logn, t.k, t.fold_c);
   const u64 psi_inv = h_powmod(t.psi, q - 2, q);                // modinv: cg_ntt.py:9-10, :91
   const u64 omega_inv = h_powmod(t.omega, q - 2, q);            // :72
   t.n_inv = h_powmod(n % q, q - 2, q);                          // :74
@@ -282,6 +316,12 @@ inline HostTables h_build_tables(u32 n, u64 q, u64 psi, bool allow_lazy) {
   u64 w = 1, wi = 1;
   for (u32 j = 0; j <= n / 2; ++j) { t.omega_pow[j] = w; t.omega_inv_pow[j] = wi; w = h_mulmod(w, t.omega, q); wi = h_mulmod(wi, omega_inv, q); }
   t.ninv_w1 = h_mulmod(t.n_inv, t.psi_inv_brv[1], q);
+  t.n2_inv = h_mulmod(t.n_inv, 2, q);
+  t.n2inv_w1 = h_mulmod(t.n2_inv, t.psi_inv_brv[1], q);
+  if (t.bc_ok) {
+    t.psi_bc = t.psi_brv; t.cyc_bc = t.cyc_brv;
+    for (u32 i = n / 2; i < n; ++i) { t.psi_bc[i] = h_mulmod(t.psi_brv[i], t.psi_brv[i], q); t.cyc_bc[i] = h_mulmod(t.cyc_brv[i], t.cyc_brv[i], q); }
+  }
   return t;
 }
 
@@ -371,6 +411,8 @@ template <typename E> inline Arith<E> h_make_arith(const HostTables& t) {
   ar.ninv = h_make_tw<E>(t.n_inv, t.q);
   ar.fninv = h_make_fused_tw<E>(t.n_inv, t);
   ar.fninv_w1 = h_make_fused_tw<E>(t.ninv_w1, t);
+  ar.bninv = h_make_fused_tw<E>(t.n2_inv, t);
+  ar.bninv_w1 = h_make_fused_tw<E>(t.n2inv_w1, t);
   return ar;
 }
 
