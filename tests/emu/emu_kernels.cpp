@@ -3,7 +3,8 @@
 // headers the gfx950 kernels are compiled from) on the CPU, one emulated thread
 // at a time with barriers between phases, so index maps, LDS layouts, table
 // semantics and lazy-reduction bounds can be checked in the GPU-less build
-// container.  Built with g++ by tests/emu/Makefile; loaded by tests/test_emu.py.
+// container.  Kernel variant, tables and constants of a fused launch and the
+// row planning come from launch_plan.h, the header the launchers take them from.  Built with g++ by tests/emu/Makefile; loaded by tests/test_emu.py.
 // It is not a product path and nothing in tiny_ntt_amd/ loads it.
 #include <stdint.h>
 #include <stddef.h>
@@ -15,71 +16,95 @@ using namespace tn;
 
 namespace {
 
-template <typename E, int LOGN, int LPT, bool LAZY, bool CIN = false>
-int fused_polymul_emu(const HostTables& t, const u64* a, const u64* b, u64* c, size_t batch, bool cyclic) {
+const std::vector<u64>& host_table(const HostTables& t, FusedTable w) {
+  switch (w) {
+    case FT_PSI_BRV: return t.psi_brv;
+    case FT_PSI_INV_BRV: return t.psi_inv_brv;
+    case FT_CYC_BRV: return t.cyc_brv;
+    case FT_CYC_INV_BRV: return t.cyc_inv_brv;
+    case FT_PSI_BC: return t.psi_bc;
+    case FT_CYC_BC: return t.cyc_bc;
+  }
+  return t.psi_brv;
+}
+
+// One workgroup of the fused kernels: every thread runs phase p, then all of them exchange through the LDS image.
+// BC: the base-case product's incomplete transform (fwd_phase / inv_phase).
+template <typename E, int LOGN, int LPT, typename Pol, bool BC = false> struct Stepper {
   typedef FusedCfg<E, LOGN, LPT> Cfg;
-  typedef Policy<E, LAZY, CIN> Pol;
   typedef typename TwOf<E>::type Tw;
-  Arith<E> ar = h_make_arith<E>(t);
-  if (cyclic) ar.fninv_w1 = ar.fninv;                      // as launch_fused_t: product in Z_q[x]/(x^n - 1)
-  const std::vector<Tw> psi_brv = h_fused_table<E>(cyclic ? t.cyc_brv : t.psi_brv, t),
-                        psi_inv_brv = h_fused_table<E>(cyclic ? t.cyc_inv_brv : t.psi_inv_brv, t);
-  std::vector<E> lds(Cfg::lds_elems());
+  static constexpr u32 T = Cfg::THREADS;
   struct Regs { E x[Cfg::R]; };
-  std::vector<Regs> xa(Cfg::THREADS), xb(Cfg::THREADS);
-
-  // host copies of what the kernel stages in LDS / prefetches into registers
-  std::vector<Tw> lds_fwd(psi_brv.begin() + Cfg::lds_tw_lo(), psi_brv.begin() + Cfg::lds_tw_hi());
-  std::vector<Tw> lds_inv(psi_inv_brv.begin() + Cfg::lds_tw_lo(), psi_inv_brv.begin() + Cfg::lds_tw_hi());
   struct Pre { Tw t[Cfg::NPRE]; };
-  std::vector<Pre> pre(Cfg::THREADS);
+  // a table in the plan's record format and the slice of it the kernel stages in LDS
+  struct Table {
+    std::vector<Tw> glob, lds;
+    Table(const HostTables& t, FusedTable w) : glob(h_fused_table<E>(host_table(t, w), t)), lds(glob.begin() + Cfg::lds_tw_lo(), glob.begin() + Cfg::lds_tw_hi()) {}
+  };
+  const Arith<E> ar;
+  std::vector<E> lds = std::vector<E>(Cfg::lds_elems());
+  std::vector<Pre> pre = std::vector<Pre>(T);        // the last phase's thread-private records of the transform stepped last
 
-  auto forward = [&](std::vector<Regs>& x) {
-    for (u32 tau = 0; tau < (u32)Cfg::THREADS; ++tau) tw_prefetch<E, Cfg>(pre[tau].t, tau, psi_brv.data());
+  template <int EX, int FROM, int TO> void exchange(std::vector<Regs>& x) {
+    for (auto& v : lds) v = (E)0xDEADBEEFu;
+    for (u32 tau = 0; tau < T; ++tau) ex_store<E, Cfg, EX, FROM>(x[tau].x, tau, lds.data());
+    for (u32 tau = 0; tau < T; ++tau) ex_load<E, Cfg, EX, TO>(x[tau].x, tau, lds.data());
+  }
+  void forward(std::vector<Regs>& x, const Table& tab) {
+    for (u32 tau = 0; tau < T; ++tau) tw_prefetch<E, Cfg>(pre[tau].t, tau, tab.glob.data());
     static_for<0, Cfg::PHASES>([&](auto p_) {
       constexpr int p = decltype(p_)::value;
-      for (u32 tau = 0; tau < (u32)Cfg::THREADS; ++tau) {
-        const TwRefs<E> tw = {psi_brv.data(), lds_fwd.data(), pre[tau].t};
-        fwd_phase<E, Cfg, Pol, p>(x[tau].x, tau, tw, ar);
+      for (u32 tau = 0; tau < T; ++tau) {
+        const TwRefs<E> tw = {tab.glob.data(), tab.lds.data(), pre[tau].t};
+        fwd_phase<E, Cfg, Pol, p, BC>(x[tau].x, tau, tw, ar);
       }
-      if constexpr (p + 1 < Cfg::PHASES) {
-        for (auto& v : lds) v = (E)0xDEADBEEFu;
-        for (u32 tau = 0; tau < (u32)Cfg::THREADS; ++tau) ex_store<E, Cfg, p, p>(x[tau].x, tau, lds.data());
-        for (u32 tau = 0; tau < (u32)Cfg::THREADS; ++tau) ex_load<E, Cfg, p, p + 1>(x[tau].x, tau, lds.data());
-      }
+      if constexpr (p + 1 < Cfg::PHASES) exchange<p, p, p + 1>(x);
     });
-  };
-  auto inverse = [&](std::vector<Regs>& x) {
-    for (u32 tau = 0; tau < (u32)Cfg::THREADS; ++tau) tw_prefetch<E, Cfg>(pre[tau].t, tau, psi_inv_brv.data());
+  }
+  void inverse(std::vector<Regs>& x, const Table& tab) {
+    for (u32 tau = 0; tau < T; ++tau) {
+      if constexpr (BC) for (auto& r : pre[tau].t) r = Tw{~(u64)0, ~(u64)0};      // records the base case's inverse must not read
+      tw_prefetch_stages<E, Cfg, Cfg::stage_begin(Cfg::PHASES - 1), BC ? LOGN - 1 : LOGN>(pre[tau].t, tau, tab.glob.data());
+    }
     static_for<0, Cfg::PHASES>([&](auto i_) {
       constexpr int p = Cfg::PHASES - 1 - decltype(i_)::value;
-      for (u32 tau = 0; tau < (u32)Cfg::THREADS; ++tau) {
-        const TwRefs<E> tw = {psi_inv_brv.data(), lds_inv.data(), pre[tau].t};
-        inv_phase<E, Cfg, Pol, p>(x[tau].x, tau, tw, ar);
+      for (u32 tau = 0; tau < T; ++tau) {
+        const TwRefs<E> tw = {tab.glob.data(), tab.lds.data(), pre[tau].t};
+        inv_phase<E, Cfg, Pol, p, BC>(x[tau].x, tau, tw, ar);
       }
-      if constexpr (p > 0) {
-        for (u32 tau = 0; tau < (u32)Cfg::THREADS; ++tau) ex_store<E, Cfg, p - 1, p>(x[tau].x, tau, lds.data());
-        for (u32 tau = 0; tau < (u32)Cfg::THREADS; ++tau) ex_load<E, Cfg, p - 1, p - 1>(x[tau].x, tau, lds.data());
-      }
+      if constexpr (p > 0) exchange<p - 1, p, p - 1>(x);
     });
-  };
+  }
+};
 
+// Same steps as polymul_fused_kernel (kernels.hip), one emulated thread at a time; BC: its base-case instantiation.
+template <typename E, int LOGN, int LPT, bool LAZY, bool CIN = false, bool BC = false>
+int fused_polymul_emu(const HostTables& t, const u64* a, const u64* b, u64* c, size_t batch, bool cyclic) {
+  typedef Policy<E, LAZY, CIN> Pol;
+  typedef Stepper<E, LOGN, LPT, Pol, BC> S;
+  typedef typename S::Cfg Cfg;
+  const FusedProductSetup<E> su = fused_product_setup(h_make_arith<E>(t), BC, cyclic);
+  S wg{su.ar};
+  const typename S::Table fwd(t, su.fwd), inv(t, su.inv);
+  std::vector<typename S::Regs> xa(S::T), xb(S::T);
   for (size_t row = 0; row < batch; ++row) {
     const size_t off = row << LOGN;
-    for (u32 tau = 0; tau < (u32)Cfg::THREADS; ++tau)
-    {
+    for (u32 tau = 0; tau < S::T; ++tau) {
       for (int r = 0; r < Cfg::R; ++r) {
         xa[tau].x[r] = (E)a[off + Cfg::jidx(0, tau, r)];
         xb[tau].x[r] = (E)b[off + Cfg::jidx(0, tau, r)];
       }
-      load_reduce<E, Cfg, Pol>(xa[tau].x, ar);
-      load_reduce<E, Cfg, Pol>(xb[tau].x, ar);
+      load_reduce<E, Cfg, Pol>(xa[tau].x, wg.ar);
+      load_reduce<E, Cfg, Pol>(xb[tau].x, wg.ar);
     }
-    forward(xa);
-    forward(xb);
-    for (u32 tau = 0; tau < (u32)Cfg::THREADS; ++tau) pointwise<E, Cfg, Pol>(xa[tau].x, xb[tau].x, ar);
-    inverse(xa);
-    for (u32 tau = 0; tau < (u32)Cfg::THREADS; ++tau)
+    wg.forward(xa, fwd);
+    wg.forward(xb, fwd);
+    for (u32 tau = 0; tau < S::T; ++tau) {
+      if constexpr (BC) basecase<Cfg, Pol>(xa[tau].x, xb[tau].x, wg.pre[tau].t + Cfg::pre_off(LOGN - 1), wg.ar);   // the zeta records came with the forward's
+      else pointwise<E, Cfg, Pol>(xa[tau].x, xb[tau].x, wg.ar);
+    }
+    wg.inverse(xa, inv);
+    for (u32 tau = 0; tau < S::T; ++tau)
       for (int r = 0; r < Cfg::R; ++r) c[off + Cfg::jidx(0, tau, r)] = xa[tau].x[r];
   }
   return 0;
@@ -88,32 +113,21 @@ int fused_polymul_emu(const HostTables& t, const u64* a, const u64* b, u64* c, s
 // Same steps as ntt_fused_kernel (kernels.hip), one emulated thread at a time.
 template <typename E, int LOGN, int LPT, bool LAZY>
 int fused_ntt_emu(const HostTables& t, int mode, const u64* in, u64* out) {
-  typedef FusedCfg<E, LOGN, LPT> Cfg;
   typedef Policy<E, LAZY> Pol;
-  typedef typename TwOf<E>::type Tw;
-  Arith<E> ar = h_make_arith<E>(t);
-  if (mode == 2) ar.fninv_w1 = ar.fninv;                    // cyc_inv_brv[1] = 1 (as launch_nttf_t does)
-  const std::vector<Tw> tab = h_fused_table<E>(mode == 2 ? t.cyc_inv_brv : (mode == 1 ? t.cyc_brv : t.psi_brv), t);
-  std::vector<Tw> lds_tab(tab.begin() + Cfg::lds_tw_lo(), tab.begin() + Cfg::lds_tw_hi());
-  std::vector<E> lds(Cfg::lds_elems());
-  struct Regs { E x[Cfg::R]; };
-  struct Pre { Tw t[Cfg::NPRE]; };
-  std::vector<Regs> x(Cfg::THREADS);
-  std::vector<Pre> pre(Cfg::THREADS);
+  typedef Stepper<E, LOGN, LPT, Pol> S;
+  typedef typename S::Cfg Cfg;
+  const FusedNttSetup<E> su = fused_ntt_setup(h_make_arith<E>(t), mode);
+  S wg{su.ar};
+  const typename S::Table tab(t, su.tab);
+  const Arith<E>& ar = wg.ar;
+  std::vector<E> nat(Cfg::N);                                 // the natural-order image
+  std::vector<typename S::Regs> x(S::T);
   constexpr int LAST = Cfg::PHASES - 1;
-  const u32 T = Cfg::THREADS;
-  for (u32 tau = 0; tau < T; ++tau) tw_prefetch<E, Cfg>(pre[tau].t, tau, tab.data());
-  if (mode == 2) {
-    for (u32 tau = 0; tau < T; ++tau) for (int r = 0; r < Cfg::R; ++r) lds[Cfg::nat_addr(Cfg::jidx(0, tau, r))] = Pol::load((E)in[Cfg::jidx(0, tau, r)], ar);
-    for (u32 tau = 0; tau < T; ++tau) for (int r = 0; r < Cfg::R; ++r) x[tau].x[r] = lds[Cfg::nat_addr(bitrev(Cfg::jidx(LAST, tau, r), LOGN))];
-    static_for<0, Cfg::PHASES>([&](auto i_) {
-      constexpr int p = Cfg::PHASES - 1 - decltype(i_)::value;
-      for (u32 tau = 0; tau < T; ++tau) { const TwRefs<E> tw = {tab.data(), lds_tab.data(), pre[tau].t}; inv_phase<E, Cfg, Pol, p>(x[tau].x, tau, tw, ar); }
-      if constexpr (p > 0) {
-        for (u32 tau = 0; tau < T; ++tau) ex_store<E, Cfg, p - 1, p>(x[tau].x, tau, lds.data());
-        for (u32 tau = 0; tau < T; ++tau) ex_load<E, Cfg, p - 1, p - 1>(x[tau].x, tau, lds.data());
-      }
-    });
+  const u32 T = S::T;
+  if (mode == FNTT_CYCLIC_INV) {
+    for (u32 tau = 0; tau < T; ++tau) for (int r = 0; r < Cfg::R; ++r) nat[Cfg::nat_addr(Cfg::jidx(0, tau, r))] = Pol::load((E)in[Cfg::jidx(0, tau, r)], ar);
+    for (u32 tau = 0; tau < T; ++tau) for (int r = 0; r < Cfg::R; ++r) x[tau].x[r] = nat[Cfg::nat_addr(bitrev(Cfg::jidx(LAST, tau, r), LOGN))];
+    wg.inverse(x, tab);
     for (u32 tau = 0; tau < T; ++tau) for (int r = 0; r < Cfg::R; ++r) out[Cfg::jidx(0, tau, r)] = x[tau].x[r];
     return 0;
   }
@@ -121,17 +135,10 @@ int fused_ntt_emu(const HostTables& t, int mode, const u64* in, u64* out) {
     const u32 j = Cfg::jidx(0, tau, r);
     x[tau].x[r] = (LAZY && r >= Cfg::R / 2) ? (E)in[j] : Pol::load((E)in[j], ar);     // as ntt_fused_kernel: only the "u" half is reduced
   }
-  static_for<0, Cfg::PHASES>([&](auto p_) {
-    constexpr int p = decltype(p_)::value;
-    for (u32 tau = 0; tau < T; ++tau) { const TwRefs<E> tw = {tab.data(), lds_tab.data(), pre[tau].t}; fwd_phase<E, Cfg, Pol, p>(x[tau].x, tau, tw, ar); }
-    if constexpr (p + 1 < Cfg::PHASES) {
-      for (u32 tau = 0; tau < T; ++tau) ex_store<E, Cfg, p, p>(x[tau].x, tau, lds.data());
-      for (u32 tau = 0; tau < T; ++tau) ex_load<E, Cfg, p, p + 1>(x[tau].x, tau, lds.data());
-    }
-  });
+  wg.forward(x, tab);
   for (u32 tau = 0; tau < T; ++tau) for (int r = 0; r < Cfg::R; ++r)
-    lds[Cfg::nat_addr(bitrev(Cfg::jidx(LAST, tau, r), LOGN))] = LAZY ? Pol::canon(x[tau].x[r], ar) : x[tau].x[r];
-  for (u32 tau = 0; tau < T; ++tau) for (int r = 0; r < Cfg::R; ++r) out[Cfg::jidx(0, tau, r)] = lds[Cfg::nat_addr(Cfg::jidx(0, tau, r))];
+    nat[Cfg::nat_addr(bitrev(Cfg::jidx(LAST, tau, r), LOGN))] = LAZY ? Pol::canon(x[tau].x[r], ar) : x[tau].x[r];
+  for (u32 tau = 0; tau < T; ++tau) for (int r = 0; r < Cfg::R; ++r) out[Cfg::jidx(0, tau, r)] = nat[Cfg::nat_addr(Cfg::jidx(0, tau, r))];
   return 0;
 }
 
@@ -375,6 +382,56 @@ int emu_fused_ntt(uint32_t n, uint64_t q, uint64_t psi, int force_canonical, int
   const HostTables t = h_build_tables(n, q, psi, !force_canonical);
   if (t.elem_bytes == 8) return t.lazy ? fused_ntt_dispatch<u64, true>(t, mode, in, out) : fused_ntt_dispatch<u64, false>(t, mode, in, out);
   return t.lazy ? fused_ntt_dispatch<u32, true>(t, mode, in, out) : fused_ntt_dispatch<u32, false>(t, mode, in, out);
+}
+
+// ---- the product kernel's base-case instantiation (tests/test_basecase.py) ----
+// 1 if a plan for (n, q, psi) runs the base-case product kernel
+int bc_enabled(uint32_t n, uint64_t q, uint64_t psi) { return h_build_tables(n, q, psi, true).bc_ok ? 1 : 0; }
+
+// exact replay of the base-case bound schedule for n = 2^logn, q = 2^k - c
+int bc_sched_ok(uint32_t logn, int k, uint64_t c) { return h_bc_sched_ok(logn, k, c) ? 1 : 0; }
+int split_sched_ok(uint32_t logn, int k, uint64_t c) { return h_split_sched_ok(logn, k, c) ? 1 : 0; }
+
+// c = a * b in Z_q[x]/(x^n + 1) (or x^n - 1: cyclic) through the base-case path; -1 if the plan does not take it
+int bc_polymul(uint32_t n, uint64_t q, uint64_t psi, const uint64_t* a, const uint64_t* b, uint64_t* c, size_t batch, int cyclic) {
+  const HostTables t = h_build_tables(n, q, psi, true);
+  if (!t.bc_ok) return -1;
+  constexpr int L = FUSED_BC_LOGN;
+  static_assert(fused_has_bc<u64, L, fused_lpt(L), true>(), "no base-case kernel is built");
+  return fused_polymul_emu<u64, L, fused_lpt(L), true, false, true>(t, a, b, c, batch, cyclic != 0);
+}
+
+// one base-case pair on raw words (the caller keeps a0, a1 within the schedule's bound): out = {c0, c1}, not reduced
+void bc_pair(int k, uint64_t c, uint64_t a0, uint64_t a1, uint64_t b0, uint64_t b1, uint64_t zeta, uint64_t* out) {
+  const u64 q = (((u64)1) << k) - c;
+  Arith<u64> ar;
+  ar.q = q; ar.k = k; ar.fold_c = (u32)c; ar.mu = 0;
+  ar.sk.mulp = (u32)1 << (k - 31);
+  ar.sk.cf = (u32)((((unsigned __int128)1) << (k + 1)) % q);
+  basecase_pair(a0, a1, b0, b1, h_make_tw64_split(zeta, q, k), ar);
+  out[0] = a0; out[1] = a1;
+}
+
+// the record split_rec() makes of b, decoded: {w, x} with w = wlo + whi 2^p, x = xlo + xhi 2^p
+void bc_split_rec(int k, uint64_t c, uint64_t b, uint64_t* out) {
+  const u64 q = (((u64)1) << k) - c;
+  const Tw64 t = split_rec(b, k, (u32)c, q);
+  out[0] = (u64)(u32)t.w + ((t.w >> 32) << (k - 31));
+  out[1] = (u64)(u32)t.wp + ((t.wp >> 32) << (k - 31));
+}
+
+// ---- row planning of the persistent launches (launch_plan.h) ----
+// which: 0 the fused kernels' policy, 1 the constant-geometry kernels'.  what: 0 chunk_bytes, 1 min_chunks, 2 enabled,
+// 3 single_rows_without_slot
+long emu_row_policy(int which, int what) {
+  const RowPolicy& p = which ? CG_ROWS : FUSED_ROWS;
+  return what == 0 ? (long)p.chunk_bytes : what == 1 ? (long)p.min_chunks : what == 2 ? (long)p.enabled : (long)p.single_rows_without_slot;
+}
+// returns 1 for dynamic rows, 0 for the fixed stride; *chunk = rows per hand-out
+int emu_plan_rows(int which, size_t row_bytes, size_t batch, size_t resident, uint32_t* chunk) {
+  const RowPlan rp = plan_rows(row_bytes, batch, resident, which ? CG_ROWS : FUSED_ROWS);
+  *chunk = rp.chunk;
+  return rp.dynamic ? 1 : 0;
 }
 
 int emu_is_lazy(uint32_t n, uint64_t q, uint64_t psi) {

@@ -13,6 +13,7 @@ int emu_fused_ntt(uint32_t n, uint64_t q, uint64_t psi, int force_canonical, int
 int emu_cg(uint32_t n, uint64_t q, uint64_t psi, int mode, const uint64_t* a, const uint64_t* b, uint64_t* out, uint64_t* trace);
 int emu_cgm(uint32_t n, uint64_t q, uint64_t psi, int mode, int group, int layout, int am, int flags, const uint64_t* a, const uint64_t* b,
             uint64_t* out, uint64_t* trace);
+int bc_polymul(uint32_t n, uint64_t q, uint64_t psi, const uint64_t* a, const uint64_t* b, uint64_t* c, size_t batch, int cyclic);
 }
 
 namespace {
@@ -50,6 +51,11 @@ int main() {
         std::fill(out.begin(), out.end(), 0);
         const int r = emu_fused_poly_mult(n, p.q, p.psi, flags, a.data(), b.data(), out.data(), 1);
         expect(r == 0 && out == ref, "fused product", n, flags, r, 0, 0);
+      }
+      if (n == base60.n && p.q == base60.q) {                                      // the plan that runs the base-case product kernel
+        std::fill(out.begin(), out.end(), 0);
+        const int r = bc_polymul(n, p.q, p.psi, a.data(), b.data(), out.data(), 1, 0);
+        expect(r == 0 && out == ref, "base-case product", n, r, 0, 0, 0);
       }
       for (int fc : {0, 1}) {
         int r = emu_fused_ntt(n, p.q, p.psi, fc, 1, a.data(), t1.data());

@@ -1,25 +1,19 @@
 """Base case of the fused product kernel's incomplete transform (fused_core.h basecase(), modarith.h split_rec(), the exact
-replay h_bc_sched_ok() in plan_tables.h), stepped on the CPU by tests/basecase/bc_emu.cpp: golden products, the oracle,
-unreduced and q - 1 inputs, the base case on arbitrary 64-bit words, and which moduli the replay accepts."""
+replay h_bc_sched_ok() in plan_tables.h), stepped on the CPU by the base-case instantiation of the product stepping in
+tests/emu/emu_kernels.cpp: golden products, the oracle, unreduced and q - 1 inputs, the base case on arbitrary 64-bit words,
+and which moduli the replay accepts."""
 import ctypes
-import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import PARAMS, P64, ROOT, ntt_prime_below, p64
-
-SRC = os.path.join(ROOT, "tests", "basecase", "bc_emu.cpp")
+from conftest import PARAMS, P64, ntt_prime_below, p64
 
 
 @pytest.fixture(scope="module")
-def bc(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("bc") / "libbc.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra", "-Wno-unknown-pragmas", "-o", so, SRC],
-                   check=True)
-    L = ctypes.CDLL(so)
+def bc(emu):
+    L = emu.lib
     u32, u64, sz, ci = ctypes.c_uint32, ctypes.c_uint64, ctypes.c_size_t, ctypes.c_int
     L.bc_enabled.argtypes = [u32, u64, u64]
     L.bc_sched_ok.argtypes = [u32, ci, u64]

@@ -35,7 +35,7 @@ def test_build_id_names_the_sources_the_library_was_built_from():
     build they belong to, so a library older than its sources (or an id older than the kernels) must not go unnoticed."""
     import hashlib
     d = os.path.join(ROOT, "tiny_ntt_amd", "csrc")
-    files = ["kernels.hip", "cg_part.hip", "capi.cpp", "multi.cpp", "modarith.h", "fused_core.h", "cg_core.h", "cg_kernel_impl.h", "dev_addr.h", "plan.h",
+    files = ["kernels.hip", "cg_part.hip", "capi.cpp", "multi.cpp", "modarith.h", "fused_core.h", "launch_plan.h", "cg_core.h", "cg_kernel_impl.h", "dev_addr.h", "plan.h",
              "plan_tables.h", "../../include/tinyntt.h"]        # the order of csrc/Makefile: BUILD_ID
     h = hashlib.sha256(b"".join(open(os.path.join(d, f), "rb").read() for f in files)).hexdigest()[:16]
     assert engine.build_id() == h, "tiny_ntt_amd/lib/libtinyntt.so is stale: run make -C tiny_ntt_amd/csrc"
@@ -140,6 +140,34 @@ def test_find_psi_returns_what_the_reference_script_returns():
         assert numtheory.find_psi(c["n"], c["q"], c["max_search"]) == c["psi"], c
     lines = []
     assert numtheory.find_psi(4096, 8380417, log_fn=lines.append) == 687 and "687" in lines[0]
+
+
+def test_plan_rows_chunks_and_dynamic_threshold(emu):
+    """Row hand-out of the persistent launches (launch_plan.h plan_rows with the launchers' own policies, probed through
+    libemu): chunk = rows in 32 KiB of one operand (at least one); dynamic exactly from min_chunks * resident * chunk rows on
+    (4 for the fused kernels, 8 for the constant-geometry ones); below that a fixed stride of single rows."""
+    L = emu.lib
+    sz, ci = ctypes.c_size_t, ctypes.c_int
+    L.emu_row_policy.argtypes = [ci, ci]; L.emu_row_policy.restype = ctypes.c_long
+    L.emu_plan_rows.argtypes = [ci, sz, sz, sz, ctypes.POINTER(ctypes.c_uint32)]
+
+    def plan(which, row_bytes, batch, resident):
+        chunk = ctypes.c_uint32()
+        return bool(L.emu_plan_rows(which, row_bytes, batch, resident, ctypes.byref(chunk))), chunk.value
+
+    FUSED, CG = 0, 1
+    assert [L.emu_row_policy(FUSED, w) for w in range(4)] == [32768, 4, 1, 0]     # no counter pair free: keeps its chunk
+    assert [L.emu_row_policy(CG, w) for w in range(4)] == [32768, 8, 1, 1]        # ... hands out single rows
+    shapes = [(4096 * 8, 1), (1024 * 4, 8), (2048 * 8, 2), (8192 * 8, 1), (256 * 4, 32)]   # (row bytes, rows per hand-out); a row above 32 KiB: one
+    for which, min_chunks in ((FUSED, 4), (CG, 8)):
+        for row_bytes, chunk in shapes:
+            for resident in (1, 3, 256, 768, 1024):
+                edge = min_chunks * resident * chunk
+                assert plan(which, row_bytes, edge, resident) == (True, chunk)
+                assert plan(which, row_bytes, edge + 1, resident) == (True, chunk)
+                assert plan(which, row_bytes, 100 * edge, resident) == (True, chunk)
+                assert plan(which, row_bytes, edge - 1, resident) == (False, 1)
+                assert plan(which, row_bytes, 1, resident) == (False, 1)
 
 
 def test_shard_rows_partition():

@@ -9,22 +9,14 @@
 // The inverse transform of a product reads the same LDS table backwards (omega^-j = -omega^(n/2-j): the butterfly's two
 // outputs change places), so one table serves both directions.
 // Per product: read a, read b, write c in HBM; 6 LDS transposes (two per transform), 12 workgroup barriers at GROUP = 8.
-// Persistent workgroups; rows handed out by a device-wide counter (plan.h: sched_acquire) or at a fixed stride.
+// Persistent workgroups; rows handed out by a device-wide counter or at a fixed stride (plan.h: launch_persistent, with
+// the CG_ROWS policy of launch_plan.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "plan.h"
 #include "cg_core.h"
 #include "dev_addr.h"
 
-#ifndef TN_CG_DYNAMIC_ROWS
-#define TN_CG_DYNAMIC_ROWS 1     // 1: persistent workgroups take their rows from a device counter (fixed stride below TN_CG_DYNAMIC_MIN rows each)
-#endif
-#ifndef TN_CG_DYNAMIC_MIN
-#define TN_CG_DYNAMIC_MIN 8
-#endif
-#ifndef TN_CG_CHUNK_BYTES
-#define TN_CG_CHUNK_BYTES 32768  // bytes of one operand handed out per atomicAdd (as TN_SCHED_CHUNK_BYTES of the fused kernels)
-#endif
 #ifndef TN_CG_NT_STREAM
 #define TN_CG_NT_STREAM 1        // 1: non-temporal loads/stores for the streamed operands (keeps L2 for the tables)
 #endif
@@ -620,37 +612,17 @@ static hipError_t launch_cg_t(const tn_plan* p, int mode, const void* a, const v
   const size_t lds_bytes = (size_t)(Sh::PINGPONG ? 2 : 1) * ((M::span(n) + 3u) & ~3u) * sizeof(E) + (size_t)(n / 2 + 1) * sizeof(Tw) + 16;   // + the next-row slots
   auto kern = cg_kernel<E, GROUP, LAYOUT, AM, BIG, CTLOGN>;
   if (lds_bytes > 160 * 1024) return hipErrorInvalidValue;
-  if (lds_bytes > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return e;
-  }
-  int per_cu = 0;
-  hipError_t qe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, (int)threads, lds_bytes);
-  if (qe != hipSuccess || per_cu < 1) per_cu = 1;
-  const size_t resident = (size_t)per_cu * (size_t)p->num_cus;
-  // dynamic hand-out in chunks of >= TN_SCHED_CHUNK_BYTES of one operand when every resident workgroup gets at least TN_CG_DYNAMIC_MIN
-  // chunks; otherwise single rows at a fixed stride
-  size_t chunk = 1;
-  if (TN_CG_DYNAMIC_ROWS) { chunk = (size_t)TN_CG_CHUNK_BYTES / ((size_t)n * sizeof(E)); if (chunk < 1) chunk = 1; }
-  const bool dynamic = TN_CG_DYNAMIC_ROWS && batch >= (size_t)TN_CG_DYNAMIC_MIN * resident * chunk;
-  if (!dynamic) chunk = 1;
-  const size_t chunks = (batch + chunk - 1) / chunk;
-  const u32 grid = (u32)(chunks < resident ? chunks : resident);
   const PlanView<E> pv = make_view<E>(p);
   if (p->general) mode |= CG_FLAG_RESTAGE;
+  return launch_persistent(p, s, reinterpret_cast<const void*>(kern), threads, lds_bytes, (size_t)n * sizeof(E), batch, CG_ROWS,
+                           [&](u32 grid, u32* sched, u32 chunk) {
 #ifdef TN_CG_STAMPS
-  if (!trace && (mode & 0xff) == CG_POLYMUL) trace = tn_cg_stamp_buffer((size_t)grid * (threads / 64) * 12 * sizeof(unsigned long long));
+    if (!trace && (mode & 0xff) == CG_POLYMUL) trace = tn_cg_stamp_buffer((size_t)grid * (threads / 64) * 12 * sizeof(unsigned long long));
 #endif
-  // rows from the device-wide counter when every resident workgroup gets at least TN_CG_DYNAMIC_MIN rows (one counter pair per launch
-  // in flight: plan.h sched_acquire; no pair free, or the stream is being captured: fixed stride)
-  SchedSlot slot;
-  if (dynamic) slot = sched_acquire(p, s);
-  if (!slot.ptr) chunk = 1;                                       // (no pair free / stream capture: fixed stride of single rows; the grid stays)
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds_bytes, s, pv.ar, logn, mode, pv.omega_pow, pv.omega_inv_pow, pv.psi_pow,
-                     pv.psi_inv_ninv, pv.psi_inv_pow, (const E*)a, (const E*)b, (E*)out, (E*)trace, (u32)batch, slot.ptr, (u32)chunk);
-  const hipError_t le = hipGetLastError();
-  sched_release(p, slot, s, le == hipSuccess);
-  return le;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds_bytes, s, pv.ar, logn, mode, pv.omega_pow, pv.omega_inv_pow, pv.psi_pow,
+                       pv.psi_inv_ninv, pv.psi_inv_pow, (const E*)a, (const E*)b, (E*)out, (E*)trace, (u32)batch, sched, chunk);
+    return hipGetLastError();
+  });
 }
 
 }  // namespace tn

@@ -52,14 +52,6 @@
 #ifndef TN_FUSED_CIN
 #define TN_FUSED_CIN 0           // 1: also build the n = 4096 / 64-bit product kernel whose bound schedule assumes canonical inputs (see launch_fused_t)
 #endif
-#ifndef TN_DYNAMIC_ROWS
-#define TN_DYNAMIC_ROWS 1        // 1: persistent workgroups take their next row from a device counter (atomicAdd) instead of a fixed
-                                 //    stride: workgroups do not all run at the same speed, and with a fixed share the slowest sets the time
-#endif
-#ifndef TN_SCHED_CHUNK_BYTES
-#define TN_SCHED_CHUNK_BYTES 32768   // dynamic scheduler: bytes of one operand handed out per atomicAdd (>= one row).  The launch's tail is up
-                                     // to one chunk long: 32 / 64 / 128 KiB measured 2.138 / 2.147 / 2.160 ms at n = 4096 / 64-bit
-#endif
 #ifndef TN_SADDR
 #define TN_SADDR 1               // 1: operand rows are addressed as scalar base (+ register offset, scalar unit) + 32-bit thread offset
 #endif
@@ -84,19 +76,6 @@
 #define TN_MARK(n)
 #endif
 namespace tn {
-
-// Row hand-out of the persistent fused kernels.  Dynamic (one atomicAdd on a device counter per chunk of rows) when the
-// launch is long enough for every resident workgroup to take at least four chunks of TN_SCHED_CHUNK_BYTES worth of rows
-// (1 row at n = 4096 / 64-bit, 8 at n = 1024 / 32-bit): a chunk that large keeps the one counter address from becoming
-// the bottleneck (one row per atomic at n = 256 ran 13x slower than a fixed stride; at n = 1024 / 24-bit, batch 16,384, 10x).
-// Otherwise a fixed stride of single rows.
-struct RowPlan { u32 chunk; bool dynamic; };
-static inline RowPlan plan_rows(size_t row_bytes, size_t batch, size_t resident) {
-  size_t want = (size_t)TN_SCHED_CHUNK_BYTES / row_bytes;
-  if (want < 1) want = 1;
-  if (TN_DYNAMIC_ROWS && batch >= 4 * resident * want) return {(u32)want, true};
-  return {1u, false};
-}
 
 // ============================================================================
 // Fused kernel
@@ -307,7 +286,7 @@ constexpr int polymul_waves() {
 
 // BC (n = 4096 / 64-bit lazy only): both forward transforms stop one stage early, basecase() replaces the last stage, the
 // pointwise product and the first inverse stage (fused_core.h); tab_fwd is then the plan's psi_bc / cyc_bc table, whose last
-// level holds the base case's zeta records, and ar.fninv / fninv_w1 carry (n/2)^-1 (launch_fused_t).
+// level holds the base case's zeta records, and ar.fninv / fninv_w1 carry (n/2)^-1 (launch_plan.h: fused_product_setup).
 template <typename E, int LOGN, int LPT, bool LAZY, bool CIN = false, bool BC = false>
 __global__ void __launch_bounds__((1 << (LOGN - LPT)), (polymul_waves<E, LOGN, LPT, LAZY>()))
 polymul_fused_kernel(const Arith<E> ar, const typename TwOf<E>::type* __restrict__ tab_fwd,
@@ -581,32 +560,17 @@ static hipError_t launch_nttf_t(const tn_plan* p, int mode, const void* in, void
   typedef typename TwOf<E>::type Tw;
   const size_t lds_bytes = (size_t)(Cfg::lds_elems() + Cfg::N) * sizeof(E) + (size_t)Cfg::lds_tw_count() * sizeof(Tw) + 16;   // + natural image, next-row slots
   const PlanView<E> pv = make_view<E>(p);
-  const void* kern = nullptr;
-  const Tw* tab = nullptr;
-  Arith<E> ar = pv.ar;
-  if (mode == FNTT_TWIST_FWD) { kern = (const void*)ntt_fused_kernel<E, LOGN, LPT, LAZY, FNTT_TWIST_FWD>; tab = pv.psi_brv; }
-  else if (mode == FNTT_CYCLIC_FWD) { kern = (const void*)ntt_fused_kernel<E, LOGN, LPT, LAZY, FNTT_CYCLIC_FWD>; tab = pv.cyc_brv; }
-  else { kern = (const void*)ntt_fused_kernel<E, LOGN, LPT, LAZY, FNTT_CYCLIC_INV>; tab = pv.cyc_inv_brv; ar.fninv_w1 = ar.fninv; }   // cyc_inv_brv[1] = 1
-  if (lds_bytes > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return e;
-  }
-  int per_cu = 0;
-  hipError_t qe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, Cfg::THREADS, lds_bytes);
-  if (qe != hipSuccess || per_cu < 1) per_cu = 1;
-  const size_t resident = (size_t)per_cu * (size_t)p->num_cus;
-  const RowPlan rp = plan_rows(Cfg::N * sizeof(E), batch, resident);
-  u32 chunk = rp.chunk;
-  const size_t chunks = (batch + chunk - 1) / chunk;
-  const u32 grid = (u32)(chunks < resident ? chunks : resident);
-  const E* in_ = (const E*)in; E* out_ = (E*)out; u32 b32 = (u32)batch;
-  SchedSlot slot;
-  if (rp.dynamic) slot = sched_acquire(p, s);
-  u32* sched = slot.ptr;
-  void* args[] = {&ar, &tab, &in_, &out_, &b32, &sched, &chunk};
-  const hipError_t le = hipLaunchKernel(kern, dim3(grid), dim3(Cfg::THREADS), args, lds_bytes, s);
-  sched_release(p, slot, s, le == hipSuccess);
-  return le;
+  auto kern = ntt_fused_kernel<E, LOGN, LPT, LAZY, FNTT_TWIST_FWD>;
+  if (mode == FNTT_CYCLIC_FWD) kern = ntt_fused_kernel<E, LOGN, LPT, LAZY, FNTT_CYCLIC_FWD>;
+  else if (mode != FNTT_TWIST_FWD) kern = ntt_fused_kernel<E, LOGN, LPT, LAZY, FNTT_CYCLIC_INV>;
+  const FusedNttSetup<E> su = fused_ntt_setup(pv.ar, mode);
+  return launch_persistent(p, s, (const void*)kern, Cfg::THREADS, lds_bytes, Cfg::N * sizeof(E), batch, FUSED_ROWS, [&](u32 grid, u32* sched, u32 chunk) {
+    const Tw* tab = fused_table(pv, su.tab);
+    const E* in_ = (const E*)in; E* out_ = (E*)out; u32 b32 = (u32)batch;
+    Arith<E> ar = su.ar;
+    void* args[] = {&ar, &tab, &in_, &out_, &b32, &sched, &chunk};
+    return hipLaunchKernel((const void*)kern, dim3(grid), dim3(Cfg::THREADS), args, lds_bytes, s);
+  });
 }
 
 template <typename E, bool LAZY>
@@ -646,42 +610,21 @@ static hipError_t launch_fused_t(const tn_plan* p, const void* a, const void* b,
   // box (same 1,963 vector instructions per wave and row, 36 instead of 8 bytes of scratch: profiles/r3_headline_ledger.txt), so the
   // shipped library accepts the promise and runs the any-word kernel.
   constexpr bool HAS_CIN = TN_FUSED_CIN && sizeof(E) == 8 && LOGN == 12 && LAZY;
-  // base case (fused_core.h basecase()): the n = 4096 / 64-bit lazy kernel, for plans whose (k, c) passes h_bc_sched_ok();
-  // measured in profiles/r4_basecase_ab.txt.  Other shapes keep the last stage and the pointwise product.
-  constexpr bool HAS_BC = sizeof(E) == 8 && LOGN == 12 && LPT == 3 && LAZY;
-  bool use_bc = false;
+  // base case: for plans whose (k, c) passes h_bc_sched_ok(), unless the promised-canonical-inputs kernel is built and applies
+  constexpr bool HAS_BC = fused_has_bc<E, LOGN, LPT, LAZY>();
+  const bool use_cin = HAS_CIN && p->canonical_inputs && !cyclic;
+  const bool use_bc = HAS_BC && p->bc_ok && !use_cin;
   auto kern = polymul_fused_kernel<E, LOGN, LPT, LAZY>;
-  if constexpr (HAS_CIN) { if (p->canonical_inputs && !cyclic) kern = polymul_fused_kernel<E, LOGN, LPT, LAZY, true>; }
-  if constexpr (HAS_BC) { if (p->bc_ok && !(HAS_CIN && p->canonical_inputs && !cyclic)) { kern = polymul_fused_kernel<E, LOGN, LPT, LAZY, false, true>; use_bc = true; } }
-  if (lds_bytes > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) return e;
-  }
-  // persistent grid: as many workgroups as can be resident (occupancy query), each looping over rows
-  int per_cu = 0;
-  hipError_t qe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, Cfg::THREADS, lds_bytes);
-  if (qe != hipSuccess || per_cu < 1) per_cu = 1;
-  const size_t resident = (size_t)per_cu * (size_t)p->num_cus;
-  const RowPlan rp = plan_rows(Cfg::N * sizeof(E), batch, resident);
-  const u32 chunk = rp.chunk;
-  const size_t chunks = (batch + chunk - 1) / chunk;
-  const u32 grid = (u32)(chunks < resident ? chunks : resident);
+  if constexpr (HAS_CIN) { if (use_cin) kern = polymul_fused_kernel<E, LOGN, LPT, LAZY, true>; }
+  if constexpr (HAS_BC) { if (use_bc) kern = polymul_fused_kernel<E, LOGN, LPT, LAZY, false, true>; }
   const PlanView<E> pv = make_view<E>(p);
-  // cyclic = product in Z_q[x]/(x^n - 1) (python_poly_mult, test_ntt_poly_mult.py:38-43): same kernel, twiddle
-  // tables of the x^n - 1 factorisation tree (HostTables::cyc_brv), whose inverse table has entry 1 equal to 1
-  Arith<E> ar = pv.ar;
-  if (use_bc) { ar.fninv = ar.bninv; ar.fninv_w1 = ar.bninv_w1; }        // the inverse runs log2(n) - 1 stages: (n/2)^-1
-  if (cyclic) ar.fninv_w1 = ar.fninv;
-  const typename TwOf<E>::type* tab_fwd = use_bc ? (cyclic ? pv.cyc_bc : pv.psi_bc) : (cyclic ? pv.cyc_brv : pv.psi_brv);
-  // one counter pair per launch in flight (ring; each pair is re-armed by the kernel that used it)
-  SchedSlot slot;
-  if (rp.dynamic) slot = sched_acquire(p, s);
-  u32* sched = slot.ptr;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(Cfg::THREADS), lds_bytes, s, ar, tab_fwd,
-                     cyclic ? pv.cyc_inv_brv : pv.psi_inv_brv, (const E*)a, (const E*)b, (E*)c, (u32)batch, sched, chunk);
-  const hipError_t le = hipGetLastError();
-  sched_release(p, slot, s, le == hipSuccess);
-  return le;
+  const FusedProductSetup<E> su = fused_product_setup(pv.ar, use_bc, cyclic);
+  return launch_persistent(p, s, reinterpret_cast<const void*>(kern), Cfg::THREADS, lds_bytes, Cfg::N * sizeof(E), batch, FUSED_ROWS,
+                           [&](u32 grid, u32* sched, u32 chunk) {
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(Cfg::THREADS), lds_bytes, s, su.ar, fused_table(pv, su.fwd), fused_table(pv, su.inv),
+                       (const E*)a, (const E*)b, (E*)c, (u32)batch, sched, chunk);
+    return hipGetLastError();
+  });
 }
 
 template <typename E, bool LAZY>

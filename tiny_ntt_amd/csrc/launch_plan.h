@@ -1,0 +1,82 @@
+// launch_plan.h — what a launch of the persistent kernels decides on the host, as plain functions without the HIP runtime:
+// which fused kernel variant, tables and constants (fused_product_setup, fused_ntt_setup) and how rows are handed out
+// (plan_rows).  The launchers (kernels.hip, cg_kernel_impl.h through plan.h: launch_persistent) and the CPU stepping of
+// tests/emu both take their decisions from here, so the CPU tests check what the launchers do.
+#pragma once
+#include <stddef.h>
+#include "fused_core.h"
+
+#ifndef TN_DYNAMIC_ROWS
+#define TN_DYNAMIC_ROWS 1        // 1: persistent workgroups take their next row from a device counter (atomicAdd) instead of a fixed
+                                 //    stride: workgroups do not all run at the same speed, and with a fixed share the slowest sets the time
+#endif
+#ifndef TN_SCHED_CHUNK_BYTES
+#define TN_SCHED_CHUNK_BYTES 32768   // dynamic scheduler: bytes of one operand handed out per atomicAdd (>= one row).  The launch's tail is up
+                                     // to one chunk long: 32 / 64 / 128 KiB measured 2.138 / 2.147 / 2.160 ms at n = 4096 / 64-bit
+#endif
+#ifndef TN_CG_DYNAMIC_ROWS
+#define TN_CG_DYNAMIC_ROWS 1     // the same switch for the constant-geometry kernels (fixed stride below TN_CG_DYNAMIC_MIN chunks each)
+#endif
+#ifndef TN_CG_DYNAMIC_MIN
+#define TN_CG_DYNAMIC_MIN 8
+#endif
+#ifndef TN_CG_CHUNK_BYTES
+#define TN_CG_CHUNK_BYTES 32768  // bytes of one operand handed out per atomicAdd (as TN_SCHED_CHUNK_BYTES of the fused kernels)
+#endif
+
+namespace tn {
+
+enum FusedNttMode { FNTT_TWIST_FWD = 0, FNTT_CYCLIC_FWD = 1, FNTT_CYCLIC_INV = 2 };
+
+// The twiddle tables of the fused kernels (HostTables / PlanView fields of the same names).
+enum FusedTable { FT_PSI_BRV, FT_PSI_INV_BRV, FT_CYC_BRV, FT_CYC_INV_BRV, FT_PSI_BC, FT_CYC_BC };
+
+// The one shape with a base-case product kernel (fused_core.h basecase(); measured in profiles/r4_basecase_ab.txt): n = 4096,
+// 64-bit lanes, lazy.  Every other shape keeps the last stage and the pointwise product.
+constexpr int FUSED_BC_LOGN = 12;
+template <typename E, int LOGN, int LPT, bool LAZY> constexpr bool fused_has_bc() {
+  return sizeof(E) == 8 && LOGN == FUSED_BC_LOGN && LPT == 3 && LAZY;
+}
+
+// Product launch.  bc: this launch runs the base-case kernel (a shape with fused_has_bc(), a plan with bc_ok, and no
+// promised-canonical-inputs kernel taking precedence: launch_fused_t).  Then the forward table is psi_bc / cyc_bc, whose last
+// level holds the base case's zeta records, and the inverse runs log2(n) - 1 stages: (n/2)^-1 in place of n^-1.
+// cyclic = product in Z_q[x]/(x^n - 1) (python_poly_mult, test_ntt_poly_mult.py:38-43): same kernel, twiddle tables of the
+// x^n - 1 factorisation tree (HostTables::cyc_brv), whose inverse table has entry 1 equal to 1.
+template <typename E> struct FusedProductSetup { bool bc; Arith<E> ar; FusedTable fwd, inv; };
+template <typename E> inline FusedProductSetup<E> fused_product_setup(const Arith<E>& ar, bool bc, bool cyclic) {
+  FusedProductSetup<E> s = {bc, ar, cyclic ? FT_CYC_BRV : FT_PSI_BRV, cyclic ? FT_CYC_INV_BRV : FT_PSI_INV_BRV};
+  if (bc) { s.ar.fninv = ar.bninv; s.ar.fninv_w1 = ar.bninv_w1; s.fwd = cyclic ? FT_CYC_BC : FT_PSI_BC; }
+  if (cyclic) s.ar.fninv_w1 = s.ar.fninv;
+  return s;
+}
+
+// Standalone transform launch (ntt_fused_kernel): the table of the mode; cg_intt's has entry 1 equal to 1.
+template <typename E> struct FusedNttSetup { Arith<E> ar; FusedTable tab; };
+template <typename E> inline FusedNttSetup<E> fused_ntt_setup(const Arith<E>& ar, int mode) {
+  FusedNttSetup<E> s = {ar, mode == FNTT_TWIST_FWD ? FT_PSI_BRV : mode == FNTT_CYCLIC_FWD ? FT_CYC_BRV : FT_CYC_INV_BRV};
+  if (mode == FNTT_CYCLIC_INV) s.ar.fninv_w1 = s.ar.fninv;
+  return s;
+}
+
+// Row hand-out of the persistent kernels.  Dynamic (one atomicAdd on a device counter per chunk of rows) when the launch is
+// long enough for every resident workgroup to take at least min_chunks chunks of chunk_bytes worth of rows (1 row at
+// n = 4096 / 64-bit, 8 at n = 1024 / 32-bit, 2 at n = 2048 / 60-bit): a chunk that large keeps the one counter address from
+// becoming the bottleneck (one row per atomic at n = 256 ran 13x slower than a fixed stride; at n = 1024 / 24-bit, batch
+// 16,384, 10x).  Otherwise a fixed stride of single rows.
+// single_rows_without_slot: what a launch does that planned dynamic rows but got no counter pair (none free, or the stream is
+// being captured: plan.h sched_acquire).  It runs at a fixed stride either way.  The fused kernels keep their chunk (a
+// workgroup then strides over chunks); the constant-geometry kernel hands out single rows.  The grid stays in both cases.
+struct RowPolicy { size_t chunk_bytes, min_chunks; bool enabled, single_rows_without_slot; };
+constexpr RowPolicy FUSED_ROWS = {TN_SCHED_CHUNK_BYTES, 4, TN_DYNAMIC_ROWS != 0, false};
+constexpr RowPolicy CG_ROWS = {TN_CG_CHUNK_BYTES, TN_CG_DYNAMIC_MIN, TN_CG_DYNAMIC_ROWS != 0, true};
+
+struct RowPlan { u32 chunk; bool dynamic; };
+inline RowPlan plan_rows(size_t row_bytes, size_t batch, size_t resident, const RowPolicy& pol) {
+  size_t want = pol.chunk_bytes / row_bytes;
+  if (want < 1) want = 1;
+  if (pol.enabled && batch >= pol.min_chunks * resident * want) return {(u32)want, true};
+  return {1u, false};
+}
+
+}  // namespace tn

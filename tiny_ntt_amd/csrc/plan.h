@@ -1,11 +1,11 @@
-// plan.h — internal plan object behind the opaque tn_plan handle, and the
-// kernel launch entry points implemented in kernels.hip.
+// plan.h — internal plan object behind the opaque tn_plan handle, the one launch path of the
+// persistent kernels (launch_persistent) and the kernel launch entry points implemented in kernels.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <atomic>
 #include <mutex>
-#include "fused_core.h"
+#include "launch_plan.h"
 
 struct tn_plan {
   tn::u32 n = 0, logn = 0;
@@ -64,7 +64,6 @@ struct tn_plan {
 
 namespace tn {
 
-enum FusedNttMode { FNTT_TWIST_FWD = 0, FNTT_CYCLIC_FWD = 1, FNTT_CYCLIC_INV = 2 };
 enum CgMode { CG_NTT_FWD = 0, CG_NTT_INV = 1, CG_POLYMUL = 2, CG_TWIST_FWD = 3, CG_CYCLIC_POLYMUL = 4 };
 
 template <typename E> struct PlanView {
@@ -102,6 +101,19 @@ template <typename E> inline PlanView<E> make_view(const tn_plan* p) {
   return v;
 }
 
+// the device table a fused launch's setup names (launch_plan.h)
+template <typename E> inline const typename TwOf<E>::type* fused_table(const PlanView<E>& v, FusedTable t) {
+  switch (t) {
+    case FT_PSI_BRV: return v.psi_brv;
+    case FT_PSI_INV_BRV: return v.psi_inv_brv;
+    case FT_CYC_BRV: return v.cyc_brv;
+    case FT_CYC_INV_BRV: return v.cyc_inv_brv;
+    case FT_PSI_BC: return v.psi_bc;
+    case FT_CYC_BC: return v.cyc_bc;
+  }
+  return nullptr;
+}
+
 // Dynamic-row-scheduler slot for one launch on stream s, or nullptr (fixed stride, always correct) when
 //   * the stream is being captured into a graph: a captured launch would bake the slot pointer into its kernel node while
 //     the ring keeps advancing, so a later replay could share a counter pair with a live launch (rows skipped); and
@@ -133,6 +145,33 @@ inline void sched_release(const tn_plan* p, const SchedSlot& s, hipStream_t stre
     ++p->sched_seq;
   }
   p->sched_mu.unlock();
+}
+
+// Launch a persistent kernel: as many workgroups as can be resident (occupancy query), each looping over rows that come in
+// chunks, from a device counter or at a fixed stride (plan_rows).  enqueue(grid, sched, chunk) launches the kernel with its
+// own arguments and returns the launch's status; sched is the launch's counter pair (one per launch in flight: ring, each
+// pair is re-armed by the kernel that used it) or nullptr for the fixed stride.
+template <typename Enqueue>
+inline hipError_t launch_persistent(const tn_plan* p, hipStream_t s, const void* kern, u32 threads, size_t lds_bytes, size_t row_bytes,
+                                    size_t batch, const RowPolicy& rows, Enqueue&& enqueue) {
+  if (lds_bytes > 48 * 1024) {
+    hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    if (e != hipSuccess) return e;
+  }
+  int per_cu = 0;
+  hipError_t qe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, (int)threads, lds_bytes);
+  if (qe != hipSuccess || per_cu < 1) per_cu = 1;
+  const size_t resident = (size_t)per_cu * (size_t)p->num_cus;
+  const RowPlan rp = plan_rows(row_bytes, batch, resident, rows);
+  u32 chunk = rp.chunk;
+  const size_t chunks = (batch + chunk - 1) / chunk;
+  const u32 grid = (u32)(chunks < resident ? chunks : resident);
+  SchedSlot slot;
+  if (rp.dynamic) slot = sched_acquire(p, s);
+  if (!slot.ptr && rows.single_rows_without_slot) chunk = 1;
+  const hipError_t le = enqueue(grid, slot.ptr, chunk);
+  sched_release(p, slot, s, le == hipSuccess);
+  return le;
 }
 
 // kernels.hip

@@ -2,7 +2,7 @@
 // Shared by capi.cpp (uploads them) and tests/emu (steps the kernels on the CPU).
 #pragma once
 #include <vector>
-#include "fused_core.h"
+#include "launch_plan.h"
 
 namespace tn {
 
@@ -255,10 +255,11 @@ inline bool h_split_sched_cin_ok(u32 logn, int k, u64 c) {
   return logn == 12 && h_split_sched_replay<FusedCfg<u64, 12, fused_lpt(12)>, true>(k, c);
 }
 
-// ... and of the product kernel with the base case (built for n = 4096 only: kernels.hip, launch_fused_t).  A (k, c) that
+// ... and of the product kernel with the base case (built for one shape only: launch_plan.h, fused_has_bc).  A (k, c) that
 // fails it keeps the kernel with the last stage and the pointwise product.
 inline bool h_bc_sched_ok(u32 logn, int k, u64 c) {
-  return logn == 12 && h_split_sched_replay<FusedCfg<u64, 12, fused_lpt(12)>, false, true>(k, c);
+  constexpr int L = FUSED_BC_LOGN;
+  return (int)logn == L && fused_has_bc<u64, L, fused_lpt(L), true>() && h_split_sched_replay<FusedCfg<u64, L, fused_lpt(L)>, false, true>(k, c);
 }
 
 // Is the split-constant lazy policy valid for this (n, k, c)?  (false too when no fused kernel is built for n)
