@@ -357,3 +357,34 @@ def test_kernel_bodies_under_address_and_ub_sanitizers():
     assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-3000:]
     m = __import__("re").search(r"(\d+) checks, 0 failures", r.stdout)
     assert m and int(m.group(1)) > 1500, r.stdout
+
+
+@pytest.mark.parametrize("n,q", __import__("chosen_rows").SHAPES)
+def test_fused_emulation_chosen_spectra_and_boundary_rows(emu, oracle, n, q):
+    """Rows whose SPECTRUM was chosen (entries 0, 1, 2, (q-1)/2, (q+1)/2, q-2, q-1: constant, equal / opposite within the butterfly
+    pairs, seeded picks), their unreduced twins a + j q, and rows with every coefficient at a fold boundary (q, 2q, 2^k, the largest
+    multiple of q in the word, ...) times a random row and times themselves (tests/chosen_rows.py): the pointwise product and the
+    base case see 0, 1 and q - 1, the load step sees its boundaries.  Every fused shape, both policies, the base-case product where a
+    plan takes it, the standalone transforms of the same rows; expected values from the oracle.
+    (GPU twin: test_gpu_parity.py::test_chosen_spectra_and_boundary_rows.)"""
+    import ctypes
+    from chosen_rows import chosen_rows, psi_of
+    from conftest import P64, p64
+    psi = psi_of(n, q)
+    cr = chosen_rows(oracle, n, q)
+    m = cr.nspec
+    for canonical in (False, True):
+        assert np.array_equal(emu.fused(n, q, psi, cr.a, cr.b, canonical=canonical), cr.ref), canonical
+        for r in range(cr.a.shape[0]):
+            assert np.array_equal(emu.fused_ntt(n, q, psi, 1, cr.a[r], canonical), cr.fwd[r]), (canonical, r)
+            assert np.array_equal(emu.fused_ntt(n, q, psi, 2, cr.a[r], canonical), cr.inv[r]), (canonical, r)
+        for r in range(2 * m):                                   # twist + forward gives the chosen spectrum back
+            assert np.array_equal(emu.fused_ntt(n, q, psi, 0, cr.a[r], canonical), cr.Sa[r % m]), (canonical, r)
+    L = emu.lib
+    L.bc_enabled.argtypes = [ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64]
+    L.bc_polymul.argtypes = [ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, P64, P64, P64, ctypes.c_size_t, ctypes.c_int]
+    assert L.bc_enabled(n, q, psi) == (1 if (n, q) == (4096, 1152921504606830593) else 0)
+    if L.bc_enabled(n, q, psi):
+        c = np.empty_like(cr.ref)
+        assert L.bc_polymul(n, q, psi, p64(np.ascontiguousarray(cr.a)), p64(np.ascontiguousarray(cr.b)), p64(c), cr.a.shape[0], 0) == 0
+        assert np.array_equal(c, cr.ref)

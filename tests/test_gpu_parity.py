@@ -640,3 +640,34 @@ def test_graph_capture_uses_the_fixed_stride_and_replays_beside_live_launches(en
             plan.poly_mult(a2, b2, out=c2, stream=s2)
         torch.cuda.synchronize()
         assert torch.equal(c, ref) and torch.equal(c2, ref2), rep
+
+
+# ---------------------------------------------------------------- chosen spectra and fold boundaries
+@pytest.mark.parametrize("n,q", __import__("chosen_rows").SHAPES)
+def test_chosen_spectra_and_boundary_rows(eng, oracle, n, q):
+    """GPU twin of test_emu.py::test_fused_emulation_chosen_spectra_and_boundary_rows: rows whose spectrum was chosen (0, 1, 2,
+    (q-1)/2, (q+1)/2, q-2, q-1; constant, equal / opposite within the butterfly pairs, seeded picks), their unreduced twins, and rows
+    at the fold boundaries (tests/chosen_rows.py), through the fused kernel, cg and cg8 under the lazy plan and the
+    PLAN_FORCE_CANONICAL plan; products against oracle.poly_mult, the standalone transforms of the same rows against
+    oracle.cg_ntt / cg_intt, and twist + forward against the chosen spectrum itself."""
+    from chosen_rows import chosen_rows, psi_of
+    psi = psi_of(n, q)
+    cr = chosen_rows(oracle, n, q)
+    m = cr.nspec
+    lazy_plan = eng.get_plan(n, q, psi, 0, 0)
+    assert lazy_plan.is_lazy and lazy_plan.has_fused
+    for flags in (0, eng.PLAN_FORCE_CANONICAL):
+        plan = eng.get_plan(n, q, psi, 0, flags)
+        assert plan.has_fused and plan.is_lazy == (flags == 0)
+        a, b = cr.a.astype(plan.dtype), cr.b.astype(plan.dtype)
+        for v in ("fused", "cg", "cg8"):
+            got = plan.poly_mult(a, b, variant=v).astype(np.uint64)
+            bad = np.nonzero((got != cr.ref).any(axis=1))[0]
+            assert bad.size == 0, f"n={n} q={q} flags={flags} {v}: rows {bad.tolist()} differ"
+            fwd = plan.ntt_forward(a, variant=v).astype(np.uint64)
+            assert np.array_equal(fwd, cr.fwd), (n, q, flags, v, np.nonzero((fwd != cr.fwd).any(axis=1))[0].tolist())
+            inv = plan.ntt_inverse(a, variant=v).astype(np.uint64)
+            assert np.array_equal(inv, cr.inv), (n, q, flags, v, np.nonzero((inv != cr.inv).any(axis=1))[0].tolist())
+        for v in ("auto", "cg", "cg8"):
+            S = plan.twisted_ntt_forward(a[:2 * m], variant=v).astype(np.uint64)
+            assert np.array_equal(S[:m], cr.Sa) and np.array_equal(S[m:], cr.Sa), (n, q, flags, v)

@@ -208,7 +208,9 @@ template <typename E, bool LAZY, bool CIN = false> struct Policy {
   }
   // Cooley-Tukey: (u, v) -> (u + w v, u - w v).  K: the lazy product is below K q (schedule constant).
   //   split: x = u + t' rides the multiply-add chain; the other output is 2u + K q - x = u + K q - t'
-  //   (mod 2^64; the true value fits by the schedule's bound).
+  //   (mod 2^64; the true value fits by the schedule's bound).  Precondition (what h_split_sched_replay checks per butterfly):
+  //   tmax(v) <= K q + 1 and u + max(tmax(v) - 1, K q) < 2^64.  Then x - u == w v (mod q), x - u < tmax(v), and v' = u + K q - (x - u).
+  //   lazy 32-bit lanes: u + K q < 2^32, K >= 2; outputs u + t and u + K q - t with t == w v (mod q), t < 2q.
   template <int K> TN_HD static void ct(E& u, E& v, Tw w, const Arith<E>& ar) {
     if constexpr (split) {
       const u64 x = mul_sp_acc(u, v, w, ar.sk);
@@ -225,7 +227,8 @@ template <typename E, bool LAZY, bool CIN = false> struct Policy {
       u = csub(s, ar.q);
     }
   }
-  // Gentleman-Sande: (u, v) -> (u + v, (u - v) w);  v < BND q
+  // Gentleman-Sande: (u, v) -> (u + v, (u - v) w);  v <= BND q, and u + BND q and u + v fit the word.  The sum is the integer u + v;
+  // the product is lazy: == (u - v) w (mod q), below tmax(u + BND q - v) (split) / 2q (32-bit lanes); canonical policy: both canonical.
   template <int BND> TN_HD static void gs(E& u, E& v, Tw w, const Arith<E>& ar) {
     if constexpr (split) {
       const E d = (u + ar.qmul[BND]) - v;

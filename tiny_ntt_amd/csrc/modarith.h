@@ -196,7 +196,7 @@ TN_HD u64 mul_tw(u64 a, Tw64 t, u64 q) {
 struct SplitK { u32 mulp, cf; };     // 2^p  and  2^(p+32) mod q (= 2c)
 // u + a w (mod q) for ANY 64-bit a, as the integer u + t' with
 //   t' = a0 wlo + a1 xlo + lo32(H) 2^p + hi32(H) cf,   H = a0 whi + a1 xhi < 2^64,
-//   t' < 2^(k+1) + (a >> 32) 2^p + 2^(k+1) + 2^32 cf   (h_sp_tmax() in plan_tables.h evaluates it exactly).
+//   t' < 2^(k+1) + (a >> 32) 2^p + 2^(k+1) + 2^32 cf   (SplitExact::tmax() in plan_tables.h evaluates it exactly).
 // The caller's bound schedule guarantees u + t' < 2^64 (SplitSched in fused_core.h, verified for the plan's
 // (k, c) on the host by h_split_sched_ok()).  mulp is a run-time value on purpose: with a literal 2^p the
 // compiler turns that multiply-add into a 64-bit shift and a 64-bit add (two instructions).
@@ -317,6 +317,8 @@ TN_HD u32 mulmod_barrett(u32 a, u32 b, u32 q, u64 mu, int k) {
   return csub(r, q);
 }
 
+// The same without the conditional subtracts.  a, b in [0,q): result == a*b (mod q), in [0, 3q); that is the value itself only
+// if 3q <= 2^32.  (pointwise_lazy, fused_core.h, feeds it fold() outputs instead and states its own bound.)
 TN_HD u32 mulmod_barrett_lazy(u32 a, u32 b, u32 q, u64 mu, int k) {
   u64 p = (u64)a * b;
   u64 q1 = p >> (k - 1);
@@ -324,6 +326,7 @@ TN_HD u32 mulmod_barrett_lazy(u32 a, u32 b, u32 q, u64 mu, int k) {
   return (u32)p - (u32)q2 * q;
 }
 
+// fold on 32-bit lanes: result == x (mod q), < 2^k + (x >> k) * c.  Needs 2^k + (2^(32-k) - 1) c <= 2^32 (the sum fits the lane).
 TN_HD u32 fold(u32 x, int k, u32 c) {
   u32 lowmask = (((u32)1) << k) - 1;
   return (x & lowmask) + (x >> k) * c;
