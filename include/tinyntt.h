@@ -143,6 +143,29 @@ tn_status tn_poly_mult_host(tn_plan *plan, const void *a, const void *b, void *c
                             tn_variant variant);
 
 /*
+ * Product with a PREPARED second operand: b is transformed once (tn_prepare_dev) and multiplied into any number of a's
+ * (tn_poly_mult_prepared_dev), which then runs two transforms per row instead of three.  For a fixed b — one key polynomial
+ * multiplied into a whole batch, or the same rows of b used by many calls.  Results are bit-identical to tn_poly_mult_dev.
+ *
+ * tn_prepare_dev: bhat[r] = prepared form of b[r] for r < rows: n words of tn_plan_elem_bytes each, the size of a row.  b may hold
+ * any word values (taken mod q).  bhat must not overlap b (TN_EINVAL).
+ * tn_poly_mult_prepared_dev: c[r] = a[r] * b[bhat_rows == 1 ? 0 : r] in Z_q[x]/(x^n+1) for r < batch.  bhat_rows must be 1 (one
+ * operand shared by every row; the kernel keeps it in registers, so it costs no memory traffic per row) or batch; anything
+ * else, and c overlapping a or bhat, is TN_EINVAL.
+ *
+ * The prepared form is OPAQUE: the negacyclic transform of b as the plan's fused product kernel holds it just before its
+ * pointwise step, in that kernel's register order.  A prepared row is valid only for plans with the same (n, q, psi, flags)
+ * and for the library build that made it (tn_build_id); do not store it across builds or interpret its words.  It serves the
+ * negacyclic product only; there is no cyclic variant.
+ * Both calls need a plan with the fused kernels (tn_plan_has_fused; TN_EUNSUPPORTED otherwise: general and omega-only plans,
+ * n < 256), enqueue on the stream and return, and may be stream-captured like every *_dev launch.  rows == 0 / batch == 0 succeed
+ * and launch nothing.  The reference has no counterpart: nwc_poly_mult transforms both operands on every call (cg_ntt.py:85-86).
+ */
+tn_status tn_prepare_dev(tn_plan *plan, const void *b, void *bhat, size_t rows, void *stream);
+tn_status tn_poly_mult_prepared_dev(tn_plan *plan, const void *a, const void *bhat, size_t bhat_rows, void *c, size_t batch,
+                                    void *stream);
+
+/*
  * The *_host entry points cut the batch into chunks that flow H2D -> kernel -> D2H on three
  * streams through a fixed set of device staging slots (copies overlap the kernels when the host
  * buffers are pinned; device staging stays bounded whatever the batch).  rows = rows per chunk,

@@ -247,6 +247,38 @@ extern "C" tn_status tn_cyclic_poly_mult_dev(tn_plan* p, const void* a, const vo
   return TN_OK;
 }
 
+// ---- prepared operand ----------------------------------------------------------
+static bool ranges_overlap(const void* x, size_t xbytes, const void* y, size_t ybytes) {
+  const char *cx = (const char*)x, *cy = (const char*)y;
+  return cx < cy + ybytes && cy < cx + xbytes;
+}
+
+extern "C" tn_status tn_prepare_dev(tn_plan* p, const void* b, void* bhat, size_t rows, void* stream) {
+  tn_status st = check_ptrs(p, b, b, bhat, rows, "tn_prepare_dev");         // NULL plan / buffers, bhat overlapping b
+  if (st) return st;
+  if (!p->has_fused) return fail(TN_EUNSUPPORTED, "tn_prepare_dev: prepared operands need a plan with the fused kernels (tn_plan_has_fused)");
+  TN_ON_DEVICE(p);
+  TN_HIP(launch_prepare(p, b, bhat, rows, pick_stream(p, stream)));
+  return TN_OK;
+}
+
+extern "C" tn_status tn_poly_mult_prepared_dev(tn_plan* p, const void* a, const void* bhat, size_t bhat_rows, void* c, size_t batch,
+                                               void* stream) {
+  const char* fn = "tn_poly_mult_prepared_dev";
+  if (!p) return fail(TN_EINVAL, std::string(fn) + ": plan is NULL");
+  if (!p->has_fused) return fail(TN_EUNSUPPORTED, std::string(fn) + ": prepared operands need a plan with the fused kernels (tn_plan_has_fused)");
+  if (batch > 0x7fffffffull) return fail(TN_EINVAL, std::string(fn) + ": batch too large for one call (max 2^31 - 1 rows)");
+  if (batch == 0) return TN_OK;
+  if (!a || !bhat || !c) return fail(TN_EINVAL, std::string(fn) + ": NULL buffer");
+  if (bhat_rows != 1 && bhat_rows != batch) return fail(TN_EINVAL, std::string(fn) + ": bhat_rows must be 1 (shared operand) or batch");
+  const size_t row_bytes = (size_t)p->n * (size_t)p->elem_bytes;
+  if (ranges_overlap(c, batch * row_bytes, a, batch * row_bytes) || ranges_overlap(c, batch * row_bytes, bhat, bhat_rows * row_bytes))
+    return fail(TN_EINVAL, std::string(fn) + ": output must not alias or overlap an input");
+  TN_ON_DEVICE(p);
+  TN_HIP(launch_polymul_prepared(p, a, bhat, bhat_rows == 1, c, batch, pick_stream(p, stream)));
+  return TN_OK;
+}
+
 extern "C" tn_status tn_pointwise_mul_dev(tn_plan* p, const void* a, const void* b, void* c, size_t batch, void* stream) {
   if (!p) return fail(TN_EINVAL, "tn_pointwise_mul_dev: plan is NULL");
   if (batch > 0xffffffffull) return fail(TN_EINVAL, "tn_pointwise_mul_dev: batch too large");

@@ -116,6 +116,10 @@ template <typename E, int LOGN_, int LPT_> struct FusedCfg {
   TN_HD static constexpr u32 jidx(int p, u32 tau, u32 r) {
     return ((tau >> pos(p)) << (pos(p) + LPT)) | (r << pos(p)) | (tau & ((1u << pos(p)) - 1u));
   }
+  // Prepared operand (prepare_fused_kernel -> polymul_prepared_kernel, kernels.hip): where register r of thread tau of the LAST
+  // phase lies within a prepared row.  Register-major, so that each of a thread's R accesses is a unit-stride access of the
+  // wave (the addressing of an operand row: ld_operand), and additive in (tau, r): prep_idx(tau, r) == prep_idx(tau, 0) + prep_idx(0, r).
+  TN_HD static constexpr u32 prep_idx(u32 tau, u32 r) { return (r << (LOGN - LPT)) | tau; }
   TN_HD static constexpr u32 ex_addr(int e, u32 j) {
     if (WB > 0 && ex_wave_local(e))
       return (j >> WSH) * (u32)region_elems() + (j & ((1u << WSH) - 1u)) + (u32)ex_pad(e) * ((j & ((1u << WSH) - 1u)) >> ex_sh(e));

@@ -75,6 +75,17 @@
 #else
 #define TN_MARK(n)
 #endif
+// This file is compiled in two slices that build in parallel (Makefile: kernels.o, kernels_prepared.o), the way cg_part.hip is:
+//   TN_KERNELS_PART 0  everything but the prepared-operand kernels
+//   TN_KERNELS_PART 1  the prepared-operand kernels and their launchers
+// Undefined (`make resources`, tools/build_variant.sh): the whole file as one translation unit.
+#ifndef TN_KERNELS_PART
+#define TN_KERNELS_MAIN 1
+#define TN_KERNELS_PREPARED 1
+#else
+#define TN_KERNELS_MAIN (TN_KERNELS_PART == 0)
+#define TN_KERNELS_PREPARED (TN_KERNELS_PART == 1)
+#endif
 namespace tn {
 
 // ============================================================================
@@ -236,7 +247,7 @@ __device__ __forceinline__ void inverse_all(E (&x)[Cfg::R], u32 tau, const TwRef
 
 template <typename E> struct alignas(2 * sizeof(E)) PairOf { E lo, hi; };
 
-#ifdef TN_FUSED_STAMPS
+#if defined(TN_FUSED_STAMPS) && TN_KERNELS_MAIN
 // DIAGNOSTIC BUILD ONLY (tools/gpu_fused_clock.py; MI355X_MICROARCH.md, DVFS give-back item 6): every workgroup of the product
 // kernel stamps s_memtime (shader cycles) and s_memrealtime (100 MHz) once before and once after its row loop into an array
 // of its own in the code object; nothing in the kernel reads it and no output depends on it.  The shipped library has no stamp.
@@ -284,6 +295,7 @@ constexpr int polymul_waves() {
   return LPT >= 4 ? 2 : (sizeof(E) == 8 && LOGN == 12 && LAZY) ? TN_POLYMUL60_WAVES : TN_FUSED_MIN_WAVES;
 }
 
+#if TN_KERNELS_MAIN
 // BC (n = 4096 / 64-bit lazy only): both forward transforms stop one stage early, basecase() replaces the last stage, the
 // pointwise product and the first inverse stage (fused_core.h); tab_fwd is then the plan's psi_bc / cyc_bc table, whose last
 // level holds the base case's zeta records, and ar.fninv / fninv_w1 carry (n/2)^-1 (launch_plan.h: fused_product_setup).
@@ -833,9 +845,269 @@ hipError_t launch_checksum(const tn_plan* p, const void* src, u64* out, size_t b
   return hipGetLastError();
 }
 
+#endif  // TN_KERNELS_MAIN
+
+#if TN_KERNELS_PREPARED
+// ============================================================================
+// Prepared operand: the product with b transformed ahead of time
+// ============================================================================
+// A prepared row holds what polymul_fused_kernel of the same plan has in xb just before pointwise() / basecase(): b's
+// negacyclic transform (stopped one stage early where the plan runs the base case), as canonical residues, word
+// FusedCfg::prep_idx(tau, r) = register r of thread tau of the last phase.  Canonical words are within every bound the
+// product's schedules assume for xb (pointwise(): any value below 14 q; basecase(): any word; 32-bit lanes fold), so the
+// product below runs on the schedules of polymul_fused_kernel unchanged.
+template <typename E, typename Cfg, bool NT>
+__device__ __forceinline__ E ld_prepared(const E* __restrict__ p, u32 row, u32 tau, int r) {
+  if constexpr (NT && TN_NT_STREAM) {      // a row streamed once: addressed like an operand row (ld_operand)
+    const TN_GLOBAL_AS E* rp = uniform_ptr(p + ((size_t)row << Cfg::LOGN) + Cfg::prep_idx(0, r));
+    return __builtin_nontemporal_load(rp + Cfg::prep_idx(tau, 0));
+  } else {
+    return p[((size_t)row << Cfg::LOGN) + Cfg::prep_idx(tau, r)];
+  }
+}
+
+// bhat[row] = prepared form of b[row].  Persistent workgroups, rows handed out and prefetched as in ntt_fused_kernel.
+// BC: the plan's product runs the base case: tab is its psi_bc table and the forward stops one stage early.
+template <typename E, int LOGN, int LPT, bool LAZY, bool BC>
+__global__ void __launch_bounds__((1 << (LOGN - LPT)), (LPT >= 4 ? 2 : TN_FUSED_MIN_WAVES))
+prepare_fused_kernel(const Arith<E> ar, const typename TwOf<E>::type* __restrict__ tab, const E* __restrict__ b, E* __restrict__ bhat, u32 batch,
+                     u32* sched, u32 chunk) {
+  typedef FusedCfg<E, LOGN, LPT> Cfg;
+  typedef Policy<E, LAZY> Pol;
+  typedef typename TwOf<E>::type Tw;
+  static_assert(Cfg::PHASES >= 2, "the last phase's twiddles are requested during the phase before it");
+  extern __shared__ __attribute__((aligned(16))) unsigned char tn_smem[];
+  E* lds = reinterpret_cast<E*>(tn_smem);
+  const u32 tau = threadIdx.x;
+  // LDS: [transpose image][staged twiddles][2 next-row slots]
+  Tw* lds_tab = reinterpret_cast<Tw*>(lds + Cfg::lds_elems());
+  u32* lds_next = reinterpret_cast<u32*>(lds_tab + Cfg::lds_tw_count());
+  for (u32 i = tau; i < (u32)Cfg::lds_tw_count(); i += Cfg::THREADS) lds_tab[i] = tab[Cfg::lds_tw_lo() + i];
+  u32 left = chunk - 1, chunk_id = blockIdx.x;            // thread 0's copies are the ones used
+  auto take_next = [&](u32 cur, u32 slot) {               // thread 0 only
+    if (left) { --left; lds_next[slot] = cur + 1; }
+    else {
+      chunk_id = sched ? gridDim.x + atomicAdd(&sched[0], 1u) : chunk_id + gridDim.x;
+      left = chunk - 1;
+      lds_next[slot] = chunk_id * chunk;
+    }
+  };
+  if (tau == 0) take_next(blockIdx.x * chunk, 1u);
+  __syncthreads();
+  u32 next = wave_uniform(lds_next[1]);
+  E xn[Cfg::R];
+  u32 row = blockIdx.x * chunk;
+  if (row < batch) {
+#pragma unroll
+    for (int r = 0; r < Cfg::R; ++r) xn[r] = ld_operand<E, Cfg>(b, row, tau, r);
+  }
+  for (u32 it = 0; row < batch; ++it) {
+    if (tau == 0) take_next(next, it & 1u);              // read back after this row's barriers
+    E x[Cfg::R];
+#pragma unroll
+    for (int r = 0; r < Cfg::R; ++r) x[r] = xn[r];
+    sched_fence();
+    if (next < batch) {
+#pragma unroll
+      for (int r = 0; r < Cfg::R; ++r) xn[r] = ld_operand<E, Cfg>(b, next, tau, r);
+    }
+    sched_fence();
+    load_reduce<E, Cfg, Pol>(x, ar);
+    {
+      Tw pre[Cfg::NPRE];
+      const TwRefs<E> tw = {tab, lds_tab, pre, nullptr, 0};
+      forward_range<E, Cfg, Pol, 0, Cfg::PHASES, false, Cfg::LOGN, BC>(x, tau, tw, ar, lds, true, tau);
+    }
+    E* out = bhat + ((size_t)row << Cfg::LOGN);
+#pragma unroll
+    for (int r = 0; r < Cfg::R; ++r) out[Cfg::prep_idx(tau, r)] = Pol::canon(x[r], ar);
+    __syncthreads();                                     // (single-wave workgroups have no barrier inside the transposes)
+    row = next;
+    next = wave_uniform(lds_next[it & 1u]);
+  }
+  if (sched && tau == 0 && atomicAdd(&sched[1], 1u) == gridDim.x - 1) { sched[0] = 0; sched[1] = 0; }
+}
+
+// c[row] = a[row] * b[SHARED ? 0 : row] with b given in prepared form: polymul_fused_kernel without b's forward transform.
+// The row loop is that kernel's: this row's a was requested during the previous row's inverse, the previous row's result is
+// stored at the top of the iteration, the twiddles of the middle phases are staged in LDS and the arithmetic constants are read
+// per phase (kernarg_arith).  a runs all its forward phases in one go (there is no second transform to share twiddles with).
+// SHARED: every row is multiplied by the ONE prepared row, which the workgroup loads into registers once before the row loop
+// (R words per thread, ordinary loads: every workgroup reads the same row, so it should stay in L2); otherwise row `row` of
+// bhat is streamed like an operand, requested at the top of the iteration and needed only after a's transform.
+#ifndef TN_PREPARED_SHARED_WAVES
+#define TN_PREPARED_SHARED_WAVES 4   // waves per SIMD of the SHARED kernel where the product kernel is built for more (n = 4096 / 64-bit lazy: 6): the
+                                     //    R resident words of the prepared row do not fit 80 registers (52 B / 212 B of scratch per lane without /
+                                     //    with the base case); at 4 (128 registers) nothing spills
+#endif
+template <typename E, int LOGN, int LPT, bool LAZY, bool SHARED>
+constexpr int prepared_waves() {
+  return SHARED && polymul_waves<E, LOGN, LPT, LAZY>() > TN_PREPARED_SHARED_WAVES ? TN_PREPARED_SHARED_WAVES : polymul_waves<E, LOGN, LPT, LAZY>();
+}
+template <typename E, int LOGN, int LPT, bool LAZY, bool BC, bool SHARED>
+__global__ void __launch_bounds__((1 << (LOGN - LPT)), (prepared_waves<E, LOGN, LPT, LAZY, SHARED>()))
+polymul_prepared_kernel(const Arith<E> ar, const typename TwOf<E>::type* __restrict__ tab_fwd,
+                        const typename TwOf<E>::type* __restrict__ tab_inv, const E* __restrict__ a, const E* __restrict__ bhat,
+                        E* __restrict__ c, u32 batch, u32* sched, u32 chunk) {
+  typedef FusedCfg<E, LOGN, LPT> Cfg;
+  typedef Policy<E, LAZY> Pol;
+  typedef typename TwOf<E>::type Tw;
+  static_assert(Cfg::PHASES >= 2, "the last phase's twiddles are requested during the phase before it");
+  extern __shared__ __attribute__((aligned(16))) unsigned char tn_smem[];
+  E* lds = reinterpret_cast<E*>(tn_smem);
+  const u32 tau = threadIdx.x;
+  Tw* lds_fwd = reinterpret_cast<Tw*>(lds + Cfg::lds_elems());
+  Tw* lds_inv = lds_fwd + Cfg::lds_tw_count();
+  u32* lds_next = reinterpret_cast<u32*>(lds_inv + Cfg::lds_tw_count());      // row index this workgroup takes next
+  for (u32 i = tau; i < (u32)Cfg::lds_tw_count(); i += Cfg::THREADS) {
+    lds_fwd[i] = tab_fwd[Cfg::lds_tw_lo() + i];
+    lds_inv[i] = tab_inv[Cfg::lds_tw_lo() + i];
+  }
+  __syncthreads();
+  E xa[Cfg::R], xb[Cfg::R], xn[Cfg::R];      // xa: the row in flight, then its result; xb: the prepared operand; xn: the next row's a
+  u32 row = blockIdx.x * chunk;
+  u32 taken = 1;                            // rows taken from the current chunk           (both workgroup-uniform: scalar registers)
+  u32 chunk_id = blockIdx.x;                // fixed-stride mode: the chunk being processed
+  if (row < batch) {
+#pragma unroll
+    for (int r = 0; r < Cfg::R; ++r) xn[r] = ld_operand<E, Cfg>(a, row, tau, r);
+    if constexpr (SHARED) {
+#pragma unroll
+      for (int r = 0; r < Cfg::R; ++r) xb[r] = ld_prepared<E, Cfg, false>(bhat, 0, tau, r);
+    }
+  }
+  // the thread-private twiddles of the last forward stage stay in registers across rows where the budget allows (polymul_fused_kernel)
+  constexpr int PRE_END = (TN_RESIDENT_TW && polymul_waves<E, LOGN, LPT, LAZY>() <= 4 && Cfg::stage_end(Cfg::PHASES - 1) - Cfg::stage_begin(Cfg::PHASES - 1) >= 2) ? Cfg::LOGN - 1 : Cfg::LOGN;
+  Tw prf[Cfg::NPRE];
+  tw_prefetch_stages<E, Cfg, PRE_END, Cfg::LOGN>(prf, tau, tab_fwd);
+  u32 prev = row;
+  bool have_c = false;
+#pragma unroll
+  for (int r = 0; r < Cfg::R; ++r) xa[r] = 0;
+  while (row < batch) {
+    const u32 zero = opaque_zero();
+    const u32 tl = opaque_copy(tau);         // thread index for global addressing within this row (see opaque_copy)
+    // one thread determines the next row now; everyone reads the answer after a's transform (barriers in between)
+    const bool in_chunk = taken != chunk;
+    taken = in_chunk ? taken + 1 : 1;
+    chunk_id = in_chunk ? chunk_id : chunk_id + gridDim.x;
+    if (tau == 0) *lds_next = in_chunk ? row + 1 : (sched ? gridDim.x + atomicAdd(&sched[0], 1u) : chunk_id) * chunk;
+    // consume this row's a first (only its loads are in flight here: the wait is exact), then issue the stores of the previous
+    // row (the first iteration writes zeros to this row's own slot, which the same thread overwrites one iteration later) and
+    // the loads of the prepared row
+    E xt[Cfg::R];
+#pragma unroll
+    for (int r = 0; r < Cfg::R; ++r) xt[r] = xn[r];
+    load_reduce<E, Cfg, Pol>(xt, ar);
+    sched_fence();
+    st_result<E, Cfg>(c, prev, tl, xa);
+    if constexpr (!SHARED) {
+#pragma unroll
+      for (int r = 0; r < Cfg::R; ++r) xb[r] = ld_prepared<E, Cfg, true>(bhat, row, tl, r);
+    }
+    sched_fence();
+#pragma unroll
+    for (int r = 0; r < Cfg::R; ++r) xa[r] = xt[r];
+    constexpr bool KARG = TN_KARG_ARITH != 0;
+    const TwRefs<E> twf = {tab_fwd, lds_fwd, prf, nullptr, zero};
+    forward_range<E, Cfg, Pol, 0, Cfg::PHASES, KARG, PRE_END, BC>(xa, tau, twf, ar, lds, true, tl);
+    __syncthreads();
+    const u32 next = wave_uniform(*lds_next);
+    // the inverse starts with the thread-private phase: request its twiddles before the product
+    Tw pre[Cfg::NPRE];
+    if constexpr (BC) {
+      basecase<Cfg, Pol>(xa, xb, prf + Cfg::pre_off(Cfg::LOGN - 1), ar);       // (the zeta records came with prf)
+      sched_fence();
+      tw_prefetch_stages<E, Cfg, Cfg::stage_begin(Cfg::PHASES - 1), Cfg::LOGN - 1>(pre, tl, tab_inv);
+    } else {
+      tw_prefetch<E, Cfg>(pre, tl, tab_inv);
+      pointwise<E, Cfg, Pol>(xa, xb, ar);
+    }
+    const TwRefs<E> twi = {tab_inv, lds_inv, pre, nullptr, zero};
+    inverse_all<E, Cfg, Pol, KARG, BC>(xa, tau, twi, ar, lds, [&]() {
+      // next row's a, requested after the inverse's own vector loads have been consumed (inverse_all).  Unconditional: after
+      // the last row this row's a is read again and dropped.
+      const u32 nrow = next < batch ? next : row;
+#pragma unroll
+      for (int r = 0; r < Cfg::R; ++r) xn[r] = ld_operand<E, Cfg>(a, nrow, tl, r);
+    });
+    prev = row;
+    have_c = true;
+    row = next;
+  }
+  if (have_c) st_result<E, Cfg>(c, prev, tau, xa);
+  // the last workgroup to run out of rows re-arms the counters for the next launch that uses this slot
+  if (sched && tau == 0 && atomicAdd(&sched[1], 1u) == gridDim.x - 1) { sched[0] = 0; sched[1] = 0; }
+}
+
+// what: nullptr -> prepare (in = b, out = bhat); otherwise the product (in = a, what = bhat, out = c)
+template <typename E, int LOGN, int LPT, bool LAZY>
+static hipError_t launch_prepared_t(const tn_plan* p, const void* in, const void* bhat, bool shared, void* out, size_t batch, hipStream_t s) {
+  typedef FusedCfg<E, LOGN, LPT> Cfg;
+  typedef typename TwOf<E>::type Tw;
+  // the base case exactly where the plan's product kernel runs it (launch_fused_t)
+  constexpr bool HAS_BC = fused_has_bc<E, LOGN, LPT, LAZY>();
+  const bool use_bc = HAS_BC && p->bc_ok;
+  const PlanView<E> pv = make_view<E>(p);
+  const FusedProductSetup<E> su = fused_product_setup(pv.ar, use_bc, false);
+  const u32 b32 = (u32)batch;
+  if (!bhat) {
+    const size_t lds_bytes = (size_t)Cfg::lds_elems() * sizeof(E) + (size_t)Cfg::lds_tw_count() * sizeof(Tw) + 16;       // + next-row slots
+    auto kern = prepare_fused_kernel<E, LOGN, LPT, LAZY, false>;
+    if constexpr (HAS_BC) { if (use_bc) kern = prepare_fused_kernel<E, LOGN, LPT, LAZY, true>; }
+    return launch_persistent(p, s, reinterpret_cast<const void*>(kern), Cfg::THREADS, lds_bytes, Cfg::N * sizeof(E), batch, FUSED_ROWS,
+                             [&](u32 grid, u32* sched, u32 chunk) {
+      hipLaunchKernelGGL(kern, dim3(grid), dim3(Cfg::THREADS), lds_bytes, s, su.ar, fused_table(pv, su.fwd), (const E*)in, (E*)out, b32, sched, chunk);
+      return hipGetLastError();
+    });
+  }
+  const size_t lds_bytes = (size_t)Cfg::lds_elems() * sizeof(E) + (size_t)2 * Cfg::lds_tw_count() * sizeof(Tw) + 16;     // + the next-row slot
+  auto kern = shared ? polymul_prepared_kernel<E, LOGN, LPT, LAZY, false, true> : polymul_prepared_kernel<E, LOGN, LPT, LAZY, false, false>;
+  if constexpr (HAS_BC) {
+    if (use_bc) kern = shared ? polymul_prepared_kernel<E, LOGN, LPT, LAZY, true, true> : polymul_prepared_kernel<E, LOGN, LPT, LAZY, true, false>;
+  }
+  return launch_persistent(p, s, reinterpret_cast<const void*>(kern), Cfg::THREADS, lds_bytes, Cfg::N * sizeof(E), batch, FUSED_ROWS,
+                           [&](u32 grid, u32* sched, u32 chunk) {
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(Cfg::THREADS), lds_bytes, s, su.ar, fused_table(pv, su.fwd), fused_table(pv, su.inv),
+                       (const E*)in, (const E*)bhat, (E*)out, b32, sched, chunk);
+    return hipGetLastError();
+  });
+}
+
+template <typename E, bool LAZY>
+static hipError_t launch_prepared_e(const tn_plan* p, const void* in, const void* bhat, bool shared, void* out, size_t batch, hipStream_t s) {
+#ifdef TN_ONLY_MAIN
+  return hipErrorInvalidValue;
+#else
+  switch (p->logn) {
+    case 8: return launch_prepared_t<E, 8, fused_lpt(8), LAZY>(p, in, bhat, shared, out, batch, s);
+    case 9: return launch_prepared_t<E, 9, fused_lpt(9), LAZY>(p, in, bhat, shared, out, batch, s);
+    case 10: return launch_prepared_t<E, 10, fused_lpt(10), LAZY>(p, in, bhat, shared, out, batch, s);
+    case 11: return launch_prepared_t<E, 11, fused_lpt(11), LAZY>(p, in, bhat, shared, out, batch, s);
+    case 12: return launch_prepared_t<E, 12, fused_lpt(12), LAZY>(p, in, bhat, shared, out, batch, s);
+    case 13: return launch_prepared_t<E, 13, fused_lpt(13), LAZY>(p, in, bhat, shared, out, batch, s);
+    default: return hipErrorInvalidValue;
+  }
+#endif
+}
+
+static hipError_t launch_prepared_any(const tn_plan* p, const void* in, const void* bhat, bool shared, void* out, size_t batch, hipStream_t s) {
+  if (batch == 0) return hipSuccess;
+  if (p->elem_bytes == 8)
+    return p->lazy ? launch_prepared_e<u64, true>(p, in, bhat, shared, out, batch, s) : launch_prepared_e<u64, false>(p, in, bhat, shared, out, batch, s);
+  return p->lazy ? launch_prepared_e<u32, true>(p, in, bhat, shared, out, batch, s) : launch_prepared_e<u32, false>(p, in, bhat, shared, out, batch, s);
+}
+
+hipError_t launch_prepare(const tn_plan* p, const void* b, void* bhat, size_t rows, hipStream_t s) {
+  return launch_prepared_any(p, b, nullptr, false, bhat, rows, s);
+}
+hipError_t launch_polymul_prepared(const tn_plan* p, const void* a, const void* bhat, bool shared, void* c, size_t batch, hipStream_t s) {
+  return launch_prepared_any(p, a, bhat, shared, c, batch, s);
+}
+#endif  // TN_KERNELS_PREPARED
 }  // namespace tn
 
-#ifdef TN_FUSED_STAMPS
+#if defined(TN_FUSED_STAMPS) && TN_KERNELS_MAIN
 extern "C" size_t tn_debug_fused_stamps(void* host, size_t max_bytes) {
   (void)hipDeviceSynchronize();
   const size_t nb = sizeof(tn::tn_fused_stamps) < max_bytes ? sizeof(tn::tn_fused_stamps) : max_bytes;

@@ -180,6 +180,9 @@ const char* fused_kernel_name(const tn_plan* p);
 const char* cg_kernel_name(const tn_plan* p, int group, int layout);
 hipError_t launch_polymul_fused(const tn_plan* p, const void* a, const void* b, void* c, size_t batch, hipStream_t s, bool cyclic = false);
 hipError_t launch_ntt_fused(const tn_plan* p, int mode, const void* in, void* out, size_t batch, hipStream_t s);
+// prepared operand (tn_prepare_dev / tn_poly_mult_prepared_dev; fused plans only).  shared: every row is multiplied by bhat's row 0
+hipError_t launch_prepare(const tn_plan* p, const void* b, void* bhat, size_t rows, hipStream_t s);
+hipError_t launch_polymul_prepared(const tn_plan* p, const void* a, const void* bhat, bool shared, void* c, size_t batch, hipStream_t s);
 hipError_t launch_cg(const tn_plan* p, int mode, int group, int layout, const void* a, const void* b, void* out,
                      void* trace, size_t batch, hipStream_t s);
 hipError_t launch_pointwise(const tn_plan* p, const void* a, const void* b, void* c, size_t batch, hipStream_t s);

@@ -38,6 +38,7 @@ EXPORTED_SYMBOLS = (
     "tn_plan_create", "tn_plan_create_omega", "tn_plan_create_general", "tn_plan_is_general", "tn_plan_destroy", "tn_plan_n", "tn_plan_q", "tn_plan_psi", "tn_plan_omega",
     "tn_plan_elem_bytes", "tn_plan_device", "tn_plan_has_fused", "tn_plan_is_lazy",
     "tn_poly_mult_dev", "tn_poly_mult_host", "tn_plan_set_host_chunk_rows", "tn_cyclic_poly_mult_dev", "tn_pointwise_mul_dev", "tn_schoolbook_dev",
+    "tn_prepare_dev", "tn_poly_mult_prepared_dev",
     "tn_plan_export_table", "tn_ntt_forward_dev", "tn_ntt_inverse_dev",
     "tn_ntt_forward_host", "tn_ntt_inverse_host", "tn_ntt_forward_trace_host", "tn_twisted_ntt_forward_dev",
     "tn_twisted_ntt_forward_host", "tn_schoolbook_host",
@@ -90,6 +91,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.tn_plan_set_host_chunk_rows.argtypes = [vp, sz]
     lib.tn_cyclic_poly_mult_dev.argtypes = [vp, vp, vp, vp, sz, ci, vp]
     lib.tn_pointwise_mul_dev.argtypes = [vp, vp, vp, vp, sz, vp]
+    lib.tn_prepare_dev.argtypes = [vp, vp, vp, sz, vp]
+    lib.tn_poly_mult_prepared_dev.argtypes = [vp, vp, vp, sz, vp, sz, vp]
     lib.tn_schoolbook_dev.argtypes = [vp, vp, vp, vp, sz, vp]
     lib.tn_plan_export_table.argtypes = [vp, ci, vp]
     for name in ("tn_ntt_forward_dev", "tn_ntt_inverse_dev", "tn_twisted_ntt_forward_dev"):
@@ -146,6 +149,14 @@ def _variant(v) -> int:
 
 def _is_torch(x) -> bool:
     return hasattr(x, "data_ptr") and hasattr(x, "is_cuda")
+
+
+class PreparedOperand:
+    """Second operand of the negacyclic product, transformed once (Plan.prepare) for any number of Plan.poly_mult_prepared
+    calls.  Opaque device words (include/tinyntt.h: tn_prepare_dev), valid only with the plan that made them."""
+
+    def __init__(self, plan, tensor, rows: int):
+        self.plan, self.tensor, self.rows = plan, tensor, int(rows)
 
 
 class Plan:
@@ -301,6 +312,40 @@ class Plan:
             raise ValueError(f"Expected {self.n} coefficients")
         c = out if out is not None else torch.empty_like(a)
         _check(self._lib, fn(self._h, a.data_ptr(), b.data_ptr(), c.data_ptr(), rows, *extra, self._stream_ptr(stream)))
+        if host:
+            res = self.to_host(c)
+            return res[0] if squeeze else res
+        return c
+
+    def prepare(self, b, out=None, stream=None) -> PreparedOperand:
+        """Transform b once (tn_prepare_dev): b is one polynomial or [rows, n], host values (taken mod q) or a device tensor."""
+        import torch
+        if not _is_torch(b):
+            b = self.to_device(b)
+        rows = self._dev_rows(b, "b")
+        t = out if out is not None else torch.empty((rows, self.n), dtype=self.torch_dtype, device=b.device)
+        if self._dev_rows(t, "out") != rows:
+            raise ValueError(f"Expected {rows} rows of {self.n} coefficients")
+        _check(self._lib, self._lib.tn_prepare_dev(self._h, b.data_ptr(), t.data_ptr(), rows, self._stream_ptr(stream)))
+        return PreparedOperand(self, t, rows)
+
+    def poly_mult_prepared(self, a, prepared: PreparedOperand, out=None, stream=None):
+        """c[r] = a[r] * b[r] in Z_q[x]/(x^n+1) with b given as Plan.prepare(b) (tn_poly_mult_prepared_dev): two transforms per
+        row instead of three.  A prepared operand of ONE row is multiplied into every row of a."""
+        import torch
+        if not isinstance(prepared, PreparedOperand):
+            raise TypeError("poly_mult_prepared: the second operand must come from Plan.prepare")
+        if prepared.plan is not self:
+            raise TinyNttError(TN_EINVAL, "poly_mult_prepared: the prepared operand belongs to another plan")
+        host = not _is_torch(a)
+        squeeze = host and np.ndim(a) == 1
+        if host:
+            a = self.to_device(a)
+        rows = self._dev_rows(a, "a")
+        c = out if out is not None else torch.empty_like(a)
+        self._dev_rows(c, "out")
+        _check(self._lib, self._lib.tn_poly_mult_prepared_dev(self._h, a.data_ptr(), prepared.tensor.data_ptr(), prepared.rows, c.data_ptr(), rows,
+                                                              self._stream_ptr(stream)))
         if host:
             res = self.to_host(c)
             return res[0] if squeeze else res
