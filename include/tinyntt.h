@@ -166,6 +166,25 @@ tn_status tn_poly_mult_prepared_dev(tn_plan *plan, const void *a, const void *bh
                                     void *stream);
 
 /*
+ * Dot product against PREPARED operands: c[r] = sum_{j < terms} a[r][j] * b[s][j] in Z_q[x]/(x^n+1), s = (bhat_sets == 1 ? 0 : r),
+ * r < batch, with ONE inverse transform per output row: terms + 1 transforms instead of the 2 * terms of `terms` calls of
+ * tn_poly_mult_prepared_dev, one result row stored, and no partial product in memory.  For sums of products against fixed
+ * operands: the digits of a key switch against its key, a row of a module-lattice matrix against a vector.
+ *
+ * a is [batch][terms][n] words (the terms of one output row are contiguous; any word values, taken mod q); bhat is
+ * [bhat_sets][terms][n], what tn_prepare_dev wrote for bhat_sets * terms rows of b (the prepared form is the same and stays
+ * opaque); bhat_sets is 1 (one set of `terms` operands for every output row) or batch; c is [batch][n], canonical residues,
+ * bit-identical to adding, mod q, the `terms` results of tn_poly_mult_dev.  terms == 1 is tn_poly_mult_prepared_dev.
+ *
+ * TN_EUNSUPPORTED: a plan without the fused kernels (as tn_poly_mult_prepared_dev).  TN_EINVAL: a NULL plan or buffer, terms == 0,
+ * bhat_sets neither 1 nor batch, batch * terms > 2^31 - 1 (the kernel indexes rows of a with 32 bits), c overlapping a's
+ * batch * terms rows or bhat's bhat_sets * terms rows.  batch == 0 succeeds and launches nothing.  Enqueues on the stream and
+ * returns; may be stream-captured.  The negacyclic product only: there is no cyclic variant, no *_host form and no tn_multi_* form.
+ */
+tn_status tn_poly_dot_prepared_dev(tn_plan *plan, const void *a, const void *bhat, size_t bhat_sets, void *c, size_t batch,
+                                   size_t terms, void *stream);
+
+/*
  * The *_host entry points cut the batch into chunks that flow H2D -> kernel -> D2H on three
  * streams through a fixed set of device staging slots (copies overlap the kernels when the host
  * buffers are pinned; device staging stays bounded whatever the batch).  rows = rows per chunk,

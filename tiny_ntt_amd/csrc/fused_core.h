@@ -637,4 +637,19 @@ TN_HD void basecase(u64 (&xa)[Cfg::R], const u64 (&xb)[Cfg::R], const Tw64* zeta
   });
 }
 
+// Sum of products (polydot_prepared_kernel, kernels.hip): acc += x mod q, term by term, as canonical residues.
+// Precondition: acc in [0, q); x is what the plan's pointwise() / basecase() returns (below PW q, ~9.75 * 2^k after the base
+// case; canonical under the canonical policy): anything Pol::canon accepts.  Postcondition: acc in [0, q), == acc + x (mod q).
+// A canonical word is below every bound the inverse schedules start from (PW q, q, the base case's), and the schedules are
+// monotone in that bound, so the inverse runs on the sum with the schedules of the single product unchanged.
+template <typename E, typename Pol>
+TN_HD E dot_accumulate_one(E acc, E x, const Arith<E>& ar) {
+  return csub((E)(acc + Pol::canon(x, ar)), ar.q);             // < 2q: fits the word (q < 2^31 / 2^63)
+}
+template <typename E, typename Cfg, typename Pol>
+TN_HD void dot_accumulate(E (&acc)[Cfg::R], const E (&x)[Cfg::R], const Arith<E>& ar) {
+#pragma unroll
+  for (int r = 0; r < Cfg::R; ++r) acc[r] = dot_accumulate_one<E, Pol>(acc[r], x[r], ar);
+}
+
 }  // namespace tn

@@ -1104,6 +1104,189 @@ hipError_t launch_prepare(const tn_plan* p, const void* b, void* bhat, size_t ro
 hipError_t launch_polymul_prepared(const tn_plan* p, const void* a, const void* bhat, bool shared, void* c, size_t batch, hipStream_t s) {
   return launch_prepared_any(p, a, bhat, shared, c, batch, s);
 }
+
+// ============================================================================
+// Prepared dot product: c[row] = sum_j a[row][j] * b[SHARED ? 0 : row][j], b given in prepared form
+// ============================================================================
+// polymul_prepared_kernel's row loop per OUTPUT row, with a run-time loop over the row's terms: every term runs one forward
+// transform and the product (pointwise() / basecase()) against its prepared row, the products are summed as canonical
+// residues (dot_accumulate, fused_core.h) and ONE inverse transform runs on the sum: terms + 1 transforms per output row.
+// The inverse is linear, and with the base case the sum is taken over residues mod y^2 - zeta, where it is linear too.
+// Issue points: term j's prepared row is requested first and term j + 1's a behind it (vector-memory operations return in
+// order, and the prepared row is needed first), both at the top of the term, before the forward's first phase, as
+// polymul_fused_kernel requests b: by the time the forward fetches its last phase's twiddles they have long arrived.  The
+// next output row's first a is requested inside the inverse (inverse_all's callback) and the result is stored at the top of
+// the next row.  SHARED: the set of `terms` prepared rows is the same for every output row; it does not fit registers for
+// terms > 1, so each term reads its row with ordinary cached loads (every workgroup reads the same rows: L2); otherwise
+// row `row * terms + j` is streamed like an operand.
+// Registers: the sum, the term in flight, its prepared row and the next term's a are 4 R live words, so every shape is built
+// for at most TN_DOT_WAVES waves per SIMD (128 registers), like the SHARED prepared kernel.
+#ifndef TN_DOT_WAVES
+#define TN_DOT_WAVES 4
+#endif
+template <typename E, int LOGN, int LPT, bool LAZY>
+constexpr int dot_waves() {
+  return polymul_waves<E, LOGN, LPT, LAZY>() > TN_DOT_WAVES ? TN_DOT_WAVES : polymul_waves<E, LOGN, LPT, LAZY>();
+}
+template <typename E, int LOGN, int LPT, bool LAZY, bool BC, bool SHARED>
+__global__ void __launch_bounds__((1 << (LOGN - LPT)), (dot_waves<E, LOGN, LPT, LAZY>()))
+polydot_prepared_kernel(const Arith<E> ar, const typename TwOf<E>::type* __restrict__ tab_fwd,
+                        const typename TwOf<E>::type* __restrict__ tab_inv, const E* __restrict__ a, const E* __restrict__ bhat,
+                        E* __restrict__ c, u32 batch, u32 terms, u32* sched, u32 chunk) {
+  typedef FusedCfg<E, LOGN, LPT> Cfg;
+  typedef Policy<E, LAZY> Pol;
+  typedef typename TwOf<E>::type Tw;
+  static_assert(Cfg::PHASES >= 2, "the last phase's twiddles are requested during the phase before it");
+  extern __shared__ __attribute__((aligned(16))) unsigned char tn_smem[];
+  E* lds = reinterpret_cast<E*>(tn_smem);
+  const u32 tau = threadIdx.x;
+  Tw* lds_fwd = reinterpret_cast<Tw*>(lds + Cfg::lds_elems());
+  Tw* lds_inv = lds_fwd + Cfg::lds_tw_count();
+  u32* lds_next = reinterpret_cast<u32*>(lds_inv + Cfg::lds_tw_count());      // output row this workgroup takes next
+  for (u32 i = tau; i < (u32)Cfg::lds_tw_count(); i += Cfg::THREADS) {
+    lds_fwd[i] = tab_fwd[Cfg::lds_tw_lo() + i];
+    lds_inv[i] = tab_inv[Cfg::lds_tw_lo() + i];
+  }
+  __syncthreads();
+  E acc[Cfg::R], xn[Cfg::R];                // acc: the sum of this row's products, then its result; xn: the next term's a
+  u32 row = blockIdx.x * chunk;
+  u32 taken = 1;                            // rows taken from the current chunk           (both workgroup-uniform: scalar registers)
+  u32 chunk_id = blockIdx.x;                // fixed-stride mode: the chunk being processed
+  if (row < batch) {
+#pragma unroll
+    for (int r = 0; r < Cfg::R; ++r) xn[r] = ld_operand<E, Cfg>(a, row * terms, tau, r);
+  }
+  // every term fetches all the thread-private twiddles of its last forward phase: keeping the last stage's in registers across
+  // rows (TN_RESIDENT_TW) spilled 36 / 44 B per lane at n = 512 / 2048 with 64-bit lazy lanes, next to the four live rows
+  constexpr int PRE_END = Cfg::LOGN;
+  Tw prf[Cfg::NPRE];
+  constexpr bool KARG = TN_KARG_ARITH != 0;
+  u32 prev = row;
+  bool have_c = false;
+#pragma unroll
+  for (int r = 0; r < Cfg::R; ++r) acc[r] = 0;
+  while (row < batch) {
+    // one thread determines the next output row now; everyone reads the answer after the last term's transform
+    const bool in_chunk = taken != chunk;
+    taken = in_chunk ? taken + 1 : 1;
+    chunk_id = in_chunk ? chunk_id : chunk_id + gridDim.x;
+    if (tau == 0) *lds_next = in_chunk ? row + 1 : (sched ? gridDim.x + atomicAdd(&sched[0], 1u) : chunk_id) * chunk;
+    const u32 arow = row * terms;            // row of a, and of a per-set bhat, of this output row's first term (< 2^31: tn_poly_dot_prepared_dev)
+    E xa[Cfg::R], xb[Cfg::R];                // the term in flight and its prepared row
+    u32 tl;
+    for (u32 j = 0;; ++j) {
+      tl = opaque_copy(tau);                 // thread index for global addressing within this term (see opaque_copy)
+      // consume this term's a first (only its loads are in flight here: the wait is exact); before the first term, issue the
+      // stores of the previous row (the first iteration writes zeros to this row's own slot, which the same thread overwrites
+      // one iteration later); then request the prepared row and, behind it, the next term's a
+      E xt[Cfg::R];
+#pragma unroll
+      for (int r = 0; r < Cfg::R; ++r) xt[r] = xn[r];
+      load_reduce<E, Cfg, Pol>(xt, ar);
+      sched_fence();
+      if (j == 0) {
+        st_result<E, Cfg>(c, prev, tl, acc);
+#pragma unroll
+        for (int r = 0; r < Cfg::R; ++r) acc[r] = 0;
+      }
+#pragma unroll
+      for (int r = 0; r < Cfg::R; ++r) xb[r] = SHARED ? ld_prepared<E, Cfg, false>(bhat, j, tl, r) : ld_prepared<E, Cfg, true>(bhat, arow + j, tl, r);
+      if (j + 1 < terms) {
+#pragma unroll
+        for (int r = 0; r < Cfg::R; ++r) xn[r] = ld_operand<E, Cfg>(a, arow + j + 1, tl, r);
+      }
+      sched_fence();
+#pragma unroll
+      for (int r = 0; r < Cfg::R; ++r) xa[r] = xt[r];
+      const TwRefs<E> twf = {tab_fwd, lds_fwd, prf, nullptr, opaque_zero()};
+      forward_range<E, Cfg, Pol, 0, Cfg::PHASES, KARG, PRE_END, BC>(xa, tau, twf, ar, lds, true, tl);
+      if (j + 1 == terms) break;             // the last term's product follows the request of the inverse's twiddles, below
+      if constexpr (BC) basecase<Cfg, Pol>(xa, xb, prf + Cfg::pre_off(Cfg::LOGN - 1), ar);       // (the zeta records came with prf)
+      else pointwise<E, Cfg, Pol>(xa, xb, ar);
+      dot_accumulate<E, Cfg, Pol>(acc, xa, ar);
+      sched_fence();
+    }
+    __syncthreads();
+    const u32 next = wave_uniform(*lds_next);
+    const u32 zero = opaque_zero();
+    // the inverse starts with the thread-private phase: request its twiddles before the last product
+    Tw pre[Cfg::NPRE];
+    if constexpr (BC) {
+      basecase<Cfg, Pol>(xa, xb, prf + Cfg::pre_off(Cfg::LOGN - 1), ar);
+      sched_fence();
+      tw_prefetch_stages<E, Cfg, Cfg::stage_begin(Cfg::PHASES - 1), Cfg::LOGN - 1>(pre, tl, tab_inv);
+    } else {
+      tw_prefetch<E, Cfg>(pre, tl, tab_inv);
+      pointwise<E, Cfg, Pol>(xa, xb, ar);
+    }
+    dot_accumulate<E, Cfg, Pol>(acc, xa, ar);
+    const TwRefs<E> twi = {tab_inv, lds_inv, pre, nullptr, zero};
+    // (the thread index through opaque_copy: the inverse's LDS addresses are recomputed per row, not kept in registers across
+    //  the row loop, where one of them was spilled at n = 4096 / 64-bit lazy with the base case and reloaded behind a vmcnt(0))
+    inverse_all<E, Cfg, Pol, KARG, BC>(acc, opaque_copy(tau), twi, ar, lds, [&]() {
+      // the next output row's first a, requested after the inverse's own vector loads have been consumed (inverse_all).
+      // Unconditional: after the last row this row's first a is read again and dropped.
+      const u32 nrow = (next < batch ? next : row) * terms;
+#pragma unroll
+      for (int r = 0; r < Cfg::R; ++r) xn[r] = ld_operand<E, Cfg>(a, nrow, tl, r);
+    });
+    prev = row;
+    have_c = true;
+    row = next;
+  }
+  if (have_c) st_result<E, Cfg>(c, prev, tau, acc);
+  // the last workgroup to run out of rows re-arms the counters for the next launch that uses this slot
+  if (sched && tau == 0 && atomicAdd(&sched[1], 1u) == gridDim.x - 1) { sched[0] = 0; sched[1] = 0; }
+}
+
+template <typename E, int LOGN, int LPT, bool LAZY>
+static hipError_t launch_dot_t(const tn_plan* p, const void* a, const void* bhat, bool shared, void* c, size_t batch, size_t terms, hipStream_t s) {
+  typedef FusedCfg<E, LOGN, LPT> Cfg;
+  typedef typename TwOf<E>::type Tw;
+  // the base case exactly where launch_prepared_t picks it
+  constexpr bool HAS_BC = fused_has_bc<E, LOGN, LPT, LAZY>();
+  const bool use_bc = HAS_BC && p->bc_ok;
+  const PlanView<E> pv = make_view<E>(p);
+  const FusedProductSetup<E> su = fused_product_setup(pv.ar, use_bc, false);
+  const u32 b32 = (u32)batch, t32 = (u32)terms;
+  const size_t lds_bytes = (size_t)Cfg::lds_elems() * sizeof(E) + (size_t)2 * Cfg::lds_tw_count() * sizeof(Tw) + 16;     // + the next-row slot
+  auto kern = shared ? polydot_prepared_kernel<E, LOGN, LPT, LAZY, false, true> : polydot_prepared_kernel<E, LOGN, LPT, LAZY, false, false>;
+  if constexpr (HAS_BC) {
+    if (use_bc) kern = shared ? polydot_prepared_kernel<E, LOGN, LPT, LAZY, true, true> : polydot_prepared_kernel<E, LOGN, LPT, LAZY, true, false>;
+  }
+  // one output row is `terms` operand rows of work: rows are handed out in chunks of at least FUSED_ROWS.chunk_bytes of a
+  return launch_persistent(p, s, reinterpret_cast<const void*>(kern), Cfg::THREADS, lds_bytes, dot_row_bytes(Cfg::N * sizeof(E), terms), batch, FUSED_ROWS,
+                           [&](u32 grid, u32* sched, u32 chunk) {
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(Cfg::THREADS), lds_bytes, s, su.ar, fused_table(pv, su.fwd), fused_table(pv, su.inv),
+                       (const E*)a, (const E*)bhat, (E*)c, b32, t32, sched, chunk);
+    return hipGetLastError();
+  });
+}
+
+template <typename E, bool LAZY>
+static hipError_t launch_dot_e(const tn_plan* p, const void* a, const void* bhat, bool shared, void* c, size_t batch, size_t terms, hipStream_t s) {
+#ifdef TN_ONLY_MAIN
+  return hipErrorInvalidValue;
+#else
+  switch (p->logn) {
+    case 8: return launch_dot_t<E, 8, fused_lpt(8), LAZY>(p, a, bhat, shared, c, batch, terms, s);
+    case 9: return launch_dot_t<E, 9, fused_lpt(9), LAZY>(p, a, bhat, shared, c, batch, terms, s);
+    case 10: return launch_dot_t<E, 10, fused_lpt(10), LAZY>(p, a, bhat, shared, c, batch, terms, s);
+    case 11: return launch_dot_t<E, 11, fused_lpt(11), LAZY>(p, a, bhat, shared, c, batch, terms, s);
+    case 12: return launch_dot_t<E, 12, fused_lpt(12), LAZY>(p, a, bhat, shared, c, batch, terms, s);
+    case 13: return launch_dot_t<E, 13, fused_lpt(13), LAZY>(p, a, bhat, shared, c, batch, terms, s);
+    default: return hipErrorInvalidValue;
+  }
+#endif
+}
+
+hipError_t launch_polydot_prepared(const tn_plan* p, const void* a, const void* bhat, bool shared, void* c, size_t batch, size_t terms, hipStream_t s) {
+  if (batch == 0) return hipSuccess;
+  if (terms == 1) return launch_polymul_prepared(p, a, bhat, shared, c, batch, s);       // the same kernel, bits and speed as a single product
+  if (p->elem_bytes == 8)
+    return p->lazy ? launch_dot_e<u64, true>(p, a, bhat, shared, c, batch, terms, s) : launch_dot_e<u64, false>(p, a, bhat, shared, c, batch, terms, s);
+  return p->lazy ? launch_dot_e<u32, true>(p, a, bhat, shared, c, batch, terms, s) : launch_dot_e<u32, false>(p, a, bhat, shared, c, batch, terms, s);
+}
 #endif  // TN_KERNELS_PREPARED
 }  // namespace tn
 

@@ -73,10 +73,15 @@ constexpr RowPolicy CG_ROWS = {TN_CG_CHUNK_BYTES, TN_CG_DYNAMIC_MIN, TN_CG_DYNAM
 
 struct RowPlan { u32 chunk; bool dynamic; };
 inline RowPlan plan_rows(size_t row_bytes, size_t batch, size_t resident, const RowPolicy& pol) {
-  size_t want = pol.chunk_bytes / row_bytes;
+  // rounded up: a chunk never holds less than chunk_bytes (the same as rounding down for every power-of-two row; a row of the
+  // prepared dot product, dot_row_bytes, need not divide chunk_bytes)
+  size_t want = (pol.chunk_bytes + row_bytes - 1) / row_bytes;
   if (want < 1) want = 1;
   if (pol.enabled && batch >= pol.min_chunks * resident * want) return {(u32)want, true};
   return {1u, false};
 }
+// Prepared dot product (polydot_prepared_kernel): one output row is `terms` operand rows of work, so that is the row size its
+// rows are planned with: a chunk stays at or above chunk_bytes of operand per atomic however short a single row is.
+inline size_t dot_row_bytes(size_t operand_row_bytes, size_t terms) { return operand_row_bytes * terms; }
 
 }  // namespace tn

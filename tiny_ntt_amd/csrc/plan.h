@@ -183,6 +183,9 @@ hipError_t launch_ntt_fused(const tn_plan* p, int mode, const void* in, void* ou
 // prepared operand (tn_prepare_dev / tn_poly_mult_prepared_dev; fused plans only).  shared: every row is multiplied by bhat's row 0
 hipError_t launch_prepare(const tn_plan* p, const void* b, void* bhat, size_t rows, hipStream_t s);
 hipError_t launch_polymul_prepared(const tn_plan* p, const void* a, const void* bhat, bool shared, void* c, size_t batch, hipStream_t s);
+// prepared dot product (tn_poly_dot_prepared_dev): c[r] = sum_j a[r][j] * b[shared ? 0 : r][j]; terms == 1 is launch_polymul_prepared
+hipError_t launch_polydot_prepared(const tn_plan* p, const void* a, const void* bhat, bool shared, void* c, size_t batch, size_t terms,
+                                   hipStream_t s);
 hipError_t launch_cg(const tn_plan* p, int mode, int group, int layout, const void* a, const void* b, void* out,
                      void* trace, size_t batch, hipStream_t s);
 hipError_t launch_pointwise(const tn_plan* p, const void* a, const void* b, void* c, size_t batch, hipStream_t s);

@@ -38,7 +38,7 @@ EXPORTED_SYMBOLS = (
     "tn_plan_create", "tn_plan_create_omega", "tn_plan_create_general", "tn_plan_is_general", "tn_plan_destroy", "tn_plan_n", "tn_plan_q", "tn_plan_psi", "tn_plan_omega",
     "tn_plan_elem_bytes", "tn_plan_device", "tn_plan_has_fused", "tn_plan_is_lazy",
     "tn_poly_mult_dev", "tn_poly_mult_host", "tn_plan_set_host_chunk_rows", "tn_cyclic_poly_mult_dev", "tn_pointwise_mul_dev", "tn_schoolbook_dev",
-    "tn_prepare_dev", "tn_poly_mult_prepared_dev",
+    "tn_prepare_dev", "tn_poly_mult_prepared_dev", "tn_poly_dot_prepared_dev",
     "tn_plan_export_table", "tn_ntt_forward_dev", "tn_ntt_inverse_dev",
     "tn_ntt_forward_host", "tn_ntt_inverse_host", "tn_ntt_forward_trace_host", "tn_twisted_ntt_forward_dev",
     "tn_twisted_ntt_forward_host", "tn_schoolbook_host",
@@ -93,6 +93,7 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.tn_pointwise_mul_dev.argtypes = [vp, vp, vp, vp, sz, vp]
     lib.tn_prepare_dev.argtypes = [vp, vp, vp, sz, vp]
     lib.tn_poly_mult_prepared_dev.argtypes = [vp, vp, vp, sz, vp, sz, vp]
+    lib.tn_poly_dot_prepared_dev.argtypes = [vp, vp, vp, sz, vp, sz, sz, vp]
     lib.tn_schoolbook_dev.argtypes = [vp, vp, vp, vp, sz, vp]
     lib.tn_plan_export_table.argtypes = [vp, ci, vp]
     for name in ("tn_ntt_forward_dev", "tn_ntt_inverse_dev", "tn_twisted_ntt_forward_dev"):
@@ -349,6 +350,44 @@ class Plan:
         if host:
             res = self.to_host(c)
             return res[0] if squeeze else res
+        return c
+
+    def poly_dot_prepared(self, a, prepared: PreparedOperand, out=None, stream=None):
+        """c[r] = sum_j a[r][j] * b[r][j] in Z_q[x]/(x^n+1) with b given as Plan.prepare(b) (tn_poly_dot_prepared_dev): one inverse
+        transform per output row.  a is (batch, terms, n), or (terms, n) for one output polynomial; the prepared operand has
+        batch * terms rows, or `terms` rows that every output row is multiplied by.  Returns (batch, n) or (n,)."""
+        import torch
+        if not isinstance(prepared, PreparedOperand):
+            raise TypeError("poly_dot_prepared: the second operand must come from Plan.prepare")
+        if prepared.plan is not self:
+            raise TinyNttError(TN_EINVAL, "poly_dot_prepared: the prepared operand belongs to another plan")
+        host = not _is_torch(a)
+        if host:
+            a = np.asarray(a)
+        if a.ndim not in (2, 3) or a.shape[-1] != self.n or a.shape[-2] == 0:
+            raise ValueError(f"Expected a of shape (batch, terms, {self.n}) or (terms, {self.n})")
+        squeeze = a.ndim == 2
+        terms = int(a.shape[-2])
+        batch = 1 if squeeze else int(a.shape[0])
+        if host:
+            a = self.to_device(a.reshape(batch * terms, self.n))
+        else:
+            if not a.is_contiguous():
+                raise TinyNttError(TN_EINVAL, f"a: need a contiguous tensor of {self.elem_bytes}-byte integers")
+            self._dev_rows(a.reshape(batch * terms, self.n), "a")
+        if prepared.rows not in (terms, batch * terms):
+            raise ValueError(f"Expected a prepared operand of {terms} or {batch * terms} rows, got {prepared.rows}")
+        sets = 1 if prepared.rows == terms else batch
+        c = out if out is not None else torch.empty((batch, self.n), dtype=self.torch_dtype, device=a.device)
+        if self._dev_rows(c, "out") != batch:
+            raise ValueError(f"Expected an output of {batch} rows of {self.n} coefficients")
+        _check(self._lib, self._lib.tn_poly_dot_prepared_dev(self._h, a.data_ptr(), prepared.tensor.data_ptr(), sets, c.data_ptr(), batch, terms,
+                                                             self._stream_ptr(stream)))
+        if host:
+            res = self.to_host(c)
+            return res[0] if squeeze else res
+        if out is None and squeeze:
+            return c[0]
         return c
 
     def cyclic_poly_mult(self, a, b, variant="auto", out=None, stream=None):
