@@ -185,6 +185,54 @@ tn_status tn_poly_dot_prepared_dev(tn_plan *plan, const void *a, const void *bha
                                    size_t terms, void *stream);
 
 /*
+ * Operands and results in the TRANSFORM DOMAIN: both operands of a sum of products prepared, the result as coefficients or
+ * as a prepared row again, and the way back from a prepared row to coefficients.  For callers whose operands are fixed or
+ * reused: c[i] = sum_j A[i][j] * s[j] for a prepared k x l matrix A over a batch of vectors s is one tn_prepare_dev of the
+ * batch's l rows per vector and k calls of tn_poly_dot_hat_dev against a shared set (l + k transforms per vector instead of
+ * the k (l + 1) of k calls of tn_poly_dot_prepared_dev); results kept prepared can be summed over several launches or fed
+ * into the next product and are turned into coefficients once, by tn_unprepare_dev.
+ *
+ * tn_unprepare_dev: x[r] = the polynomial whose prepared form is xhat[r], r < rows: the inverse of tn_prepare_dev.  Natural
+ * order, canonical residues: tn_unprepare_dev(tn_prepare_dev(x)) == x mod q, and tn_prepare_dev(tn_unprepare_dev(xhat)) ==
+ * xhat word for word for rows the library wrote.  x must not overlap xhat (TN_EINVAL).
+ *
+ * tn_poly_dot_hat_dev: out[r] = sum_{j < terms} a[r][j] * b[s][j] in Z_q[x]/(x^n+1), s = (bhat_sets == 1 ? 0 : r), r < batch, with
+ * BOTH operands prepared: ahat is [batch][terms][n], bhat is [bhat_sets][terms][n], both as tn_prepare_dev or this function
+ * wrote them; bhat_sets is 1 (one set of `terms` rows for every output row) or batch.
+ *   out_prepared == 0: out is [batch][n] coefficients, canonical residues; the one inverse transform runs in the same launch.
+ *                      Bit-identical to tn_poly_dot_prepared_dev on the un-prepared a, i.e. to adding, mod q, the `terms`
+ *                      results of tn_poly_mult_dev.
+ *   out_prepared == 1: out is [batch][n] prepared words and no transform runs at all: word for word what tn_prepare_dev
+ *                      writes for that coefficient result.
+ *
+ * The prepared form stays OPAQUE (see tn_prepare_dev), with one property callers may rely on: it is ADDITIVE.  The word-wise
+ * sum mod q of two prepared rows of one plan is the prepared row of the sum of the two polynomials, for every plan: the
+ * prepared form is a linear image of the polynomial over Z_q (its complete negacyclic transform, or, where the plan's product
+ * kernel stops one stage early, its residues modulo the factors y^2 - zeta of x^n + 1), stored as canonical residues.
+ * A prepared word the library did not write, in particular one >= q, gives an unspecified result (never an out-of-bounds
+ * access: no address depends on data).  Sums must therefore be reduced below q before they are passed back.
+ *
+ * When to use which (MI355X, profiles/hat_domain_ab.txt; slowest repeat of the new call against the fastest of the old):
+ *   - a already prepared (a fixed operand, or a result kept prepared): tn_poly_dot_hat_dev is faster than tn_poly_dot_prepared_dev at
+ *     every measured point: x 0.59 - 0.66 of its time at n = 4096 / 60-bit, x 0.62 - 0.80 at n = 1024 / 24-bit (terms 2 - 4,
+ *     coefficients out), x 0.42 - 0.71 with out_prepared = 1.
+ *   - matrix times vector with the prepare of the vectors counted: faster at k = l = 4 (x 0.74 at n = 4096 / 60-bit, x 0.83 at
+ *     n = 1024 / 24-bit) and at k = l = 2, n = 4096 / 60-bit (x 0.92); SLOWER at k = l = 2, n = 1024 / 24-bit (x 1.08: three short
+ *     launches against two): there keep calling tn_poly_dot_prepared_dev.
+ *   - tn_unprepare_dev costs what tn_ntt_inverse_dev does (x 0.99 / x 0.88); against tn_prepare_dev it is x 1.08 at n = 4096 / 60-bit
+ *     (not faster) and x 0.94 at n = 1024 / 24-bit.
+ *
+ * TN_EUNSUPPORTED: a plan without the fused kernels (as tn_poly_dot_prepared_dev).  TN_EINVAL: a NULL plan or buffer, terms == 0,
+ * bhat_sets neither 1 nor batch, batch * terms > 2^31 - 1 (rows are indexed with 32 bits), out_prepared neither 0 nor 1, out
+ * overlapping ahat's batch * terms rows or bhat's bhat_sets * terms rows (byte ranges).  batch == 0 / rows == 0 succeed and
+ * launch nothing.  Both calls enqueue on the stream and return, and may be stream-captured (a captured launch hands rows out
+ * at the fixed stride).  The negacyclic product only: no cyclic variant, no *_host form and no tn_multi_* form.
+ */
+tn_status tn_unprepare_dev(tn_plan *plan, const void *xhat, void *x, size_t rows, void *stream);
+tn_status tn_poly_dot_hat_dev(tn_plan *plan, const void *ahat, const void *bhat, size_t bhat_sets, void *out, size_t batch,
+                              size_t terms, int out_prepared, void *stream);
+
+/*
  * The *_host entry points cut the batch into chunks that flow H2D -> kernel -> D2H on three
  * streams through a fixed set of device staging slots (copies overlap the kernels when the host
  * buffers are pinned; device staging stays bounded whatever the batch).  rows = rows per chunk,

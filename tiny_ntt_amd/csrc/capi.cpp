@@ -299,6 +299,37 @@ extern "C" tn_status tn_poly_dot_prepared_dev(tn_plan* p, const void* a, const v
   return TN_OK;
 }
 
+// ---- transform domain: prepared rows in; coefficients or prepared rows out -----------
+extern "C" tn_status tn_unprepare_dev(tn_plan* p, const void* xhat, void* x, size_t rows, void* stream) {
+  tn_status st = check_ptrs(p, xhat, xhat, x, rows, "tn_unprepare_dev");     // NULL plan / buffers, x overlapping xhat
+  if (st) return st;
+  if (!p->has_fused) return fail(TN_EUNSUPPORTED, "tn_unprepare_dev: prepared operands need a plan with the fused kernels (tn_plan_has_fused)");
+  TN_ON_DEVICE(p);
+  TN_HIP(launch_unprepare(p, xhat, x, rows, pick_stream(p, stream)));
+  return TN_OK;
+}
+
+extern "C" tn_status tn_poly_dot_hat_dev(tn_plan* p, const void* ahat, const void* bhat, size_t bhat_sets, void* out, size_t batch,
+                                         size_t terms, int out_prepared, void* stream) {
+  const char* fn = "tn_poly_dot_hat_dev";
+  if (!p) return fail(TN_EINVAL, std::string(fn) + ": plan is NULL");
+  if (!p->has_fused) return fail(TN_EUNSUPPORTED, std::string(fn) + ": prepared operands need a plan with the fused kernels (tn_plan_has_fused)");
+  if (terms == 0) return fail(TN_EINVAL, std::string(fn) + ": terms must be at least 1");
+  if (out_prepared != 0 && out_prepared != 1) return fail(TN_EINVAL, std::string(fn) + ": out_prepared must be 0 (coefficients) or 1 (prepared rows)");
+  // (the kernel indexes rows of ahat with 32 bits; the division keeps batch * terms from wrapping size_t first)
+  if (batch > 0x7fffffffull || terms > 0x7fffffffull || (batch && terms > 0x7fffffffull / batch))
+    return fail(TN_EINVAL, std::string(fn) + ": batch * terms too large for one call (max 2^31 - 1 rows of ahat)");
+  if (batch == 0) return TN_OK;
+  if (!ahat || !bhat || !out) return fail(TN_EINVAL, std::string(fn) + ": NULL buffer");
+  if (bhat_sets != 1 && bhat_sets != batch) return fail(TN_EINVAL, std::string(fn) + ": bhat_sets must be 1 (one set of operands for every row) or batch");
+  const size_t row_bytes = (size_t)p->n * (size_t)p->elem_bytes;
+  if (ranges_overlap(out, batch * row_bytes, ahat, batch * terms * row_bytes) || ranges_overlap(out, batch * row_bytes, bhat, bhat_sets * terms * row_bytes))
+    return fail(TN_EINVAL, std::string(fn) + ": output must not alias or overlap an input");
+  TN_ON_DEVICE(p);
+  TN_HIP(launch_polydot_hat(p, ahat, bhat, bhat_sets == 1, out, batch, terms, out_prepared == 1, pick_stream(p, stream)));
+  return TN_OK;
+}
+
 extern "C" tn_status tn_pointwise_mul_dev(tn_plan* p, const void* a, const void* b, void* c, size_t batch, void* stream) {
   if (!p) return fail(TN_EINVAL, "tn_pointwise_mul_dev: plan is NULL");
   if (batch > 0xffffffffull) return fail(TN_EINVAL, "tn_pointwise_mul_dev: batch too large");

@@ -637,6 +637,23 @@ TN_HD void basecase(u64 (&xa)[Cfg::R], const u64 (&xb)[Cfg::R], const Tw64* zeta
   });
 }
 
+// basecase() for a caller that keeps the zeta records elsewhere and has work to do between pairs (polydot_hat_kernel): pair i's
+// record is zeta[i * ZSTRIDE], read just before the pair, and after_pair(integral_constant i) runs once the pair is done, when
+// registers 2i and 2i + 1 of xa hold its product and those of xb are dead.
+template <typename Cfg, typename Pol, int ZSTRIDE, typename F>
+TN_HD void basecase_each(u64 (&xa)[Cfg::R], const u64 (&xb)[Cfg::R], const Tw64* zeta, const Arith<u64>& ar, F&& after_pair) {
+  typedef SchedOf<Pol, Cfg, true> SO;
+  static_assert(Pol::split && Cfg::pos(Cfg::PHASES - 1) == 0, "base case: split policy, pairs in neighbouring registers");
+  static_for<0, Cfg::R / 2>([&](auto i_) {
+    constexpr int r = 2 * decltype(i_)::value;
+    if constexpr (SO::bc_fold(r)) xa[r] = fold(xa[r], ar.k, ar.fold_c);
+    if constexpr (SO::bc_fold(r + 1)) xa[r + 1] = fold(xa[r + 1], ar.k, ar.fold_c);
+    basecase_pair(xa[r], xa[r + 1], xb[r], xb[r + 1], zeta[(r / 2) * ZSTRIDE], ar);
+    sched_fence();                     // one pair in flight at a time: bounds the live temporaries
+    after_pair(i_);
+  });
+}
+
 // Sum of products (polydot_prepared_kernel, kernels.hip): acc += x mod q, term by term, as canonical residues.
 // Precondition: acc in [0, q); x is what the plan's pointwise() / basecase() returns (below PW q, ~9.75 * 2^k after the base
 // case; canonical under the canonical policy): anything Pol::canon accepts.  Postcondition: acc in [0, q), == acc + x (mod q).

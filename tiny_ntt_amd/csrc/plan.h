@@ -186,6 +186,10 @@ hipError_t launch_polymul_prepared(const tn_plan* p, const void* a, const void* 
 // prepared dot product (tn_poly_dot_prepared_dev): c[r] = sum_j a[r][j] * b[shared ? 0 : r][j]; terms == 1 is launch_polymul_prepared
 hipError_t launch_polydot_prepared(const tn_plan* p, const void* a, const void* bhat, bool shared, void* c, size_t batch, size_t terms,
                                    hipStream_t s);
+// transform domain (tn_unprepare_dev / tn_poly_dot_hat_dev): prepared rows in; coefficients out, or prepared rows (out_prepared)
+hipError_t launch_unprepare(const tn_plan* p, const void* xhat, void* x, size_t rows, hipStream_t s);
+hipError_t launch_polydot_hat(const tn_plan* p, const void* ahat, const void* bhat, bool shared, void* out, size_t batch, size_t terms,
+                              bool out_prepared, hipStream_t s);
 hipError_t launch_cg(const tn_plan* p, int mode, int group, int layout, const void* a, const void* b, void* out,
                      void* trace, size_t batch, hipStream_t s);
 hipError_t launch_pointwise(const tn_plan* p, const void* a, const void* b, void* c, size_t batch, hipStream_t s);

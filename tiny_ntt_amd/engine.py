@@ -38,7 +38,7 @@ EXPORTED_SYMBOLS = (
     "tn_plan_create", "tn_plan_create_omega", "tn_plan_create_general", "tn_plan_is_general", "tn_plan_destroy", "tn_plan_n", "tn_plan_q", "tn_plan_psi", "tn_plan_omega",
     "tn_plan_elem_bytes", "tn_plan_device", "tn_plan_has_fused", "tn_plan_is_lazy",
     "tn_poly_mult_dev", "tn_poly_mult_host", "tn_plan_set_host_chunk_rows", "tn_cyclic_poly_mult_dev", "tn_pointwise_mul_dev", "tn_schoolbook_dev",
-    "tn_prepare_dev", "tn_poly_mult_prepared_dev", "tn_poly_dot_prepared_dev",
+    "tn_prepare_dev", "tn_poly_mult_prepared_dev", "tn_poly_dot_prepared_dev", "tn_unprepare_dev", "tn_poly_dot_hat_dev",
     "tn_plan_export_table", "tn_ntt_forward_dev", "tn_ntt_inverse_dev",
     "tn_ntt_forward_host", "tn_ntt_inverse_host", "tn_ntt_forward_trace_host", "tn_twisted_ntt_forward_dev",
     "tn_twisted_ntt_forward_host", "tn_schoolbook_host",
@@ -94,6 +94,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.tn_prepare_dev.argtypes = [vp, vp, vp, sz, vp]
     lib.tn_poly_mult_prepared_dev.argtypes = [vp, vp, vp, sz, vp, sz, vp]
     lib.tn_poly_dot_prepared_dev.argtypes = [vp, vp, vp, sz, vp, sz, sz, vp]
+    lib.tn_unprepare_dev.argtypes = [vp, vp, vp, sz, vp]
+    lib.tn_poly_dot_hat_dev.argtypes = [vp, vp, vp, sz, vp, sz, sz, ci, vp]
     lib.tn_schoolbook_dev.argtypes = [vp, vp, vp, vp, sz, vp]
     lib.tn_plan_export_table.argtypes = [vp, ci, vp]
     for name in ("tn_ntt_forward_dev", "tn_ntt_inverse_dev", "tn_twisted_ntt_forward_dev"):
@@ -389,6 +391,48 @@ class Plan:
         if out is None and squeeze:
             return c[0]
         return c
+
+    def _own_prepared(self, prepared, fn, which):
+        if not isinstance(prepared, PreparedOperand):
+            raise TypeError(f"{fn}: the {which} must come from Plan.prepare (or Plan.poly_dot_hat with keep_prepared)")
+        if prepared.plan is not self:
+            raise TinyNttError(TN_EINVAL, f"{fn}: the prepared operand belongs to another plan")
+
+    def unprepare(self, prepared: PreparedOperand, out=None, stream=None):
+        """The polynomials whose prepared form `prepared` holds (tn_unprepare_dev): a device tensor (rows, n) of canonical residues,
+        the inverse of Plan.prepare."""
+        import torch
+        self._own_prepared(prepared, "unprepare", "operand")
+        rows = prepared.rows
+        x = out if out is not None else torch.empty((rows, self.n), dtype=self.torch_dtype, device=prepared.tensor.device)
+        if self._dev_rows(x, "out") != rows:
+            raise ValueError(f"Expected an output of {rows} rows of {self.n} coefficients")
+        _check(self._lib, self._lib.tn_unprepare_dev(self._h, prepared.tensor.data_ptr(), x.data_ptr(), rows, self._stream_ptr(stream)))
+        return x
+
+    def poly_dot_hat(self, a_prepared: PreparedOperand, b_prepared: PreparedOperand, terms=1, out=None, stream=None, keep_prepared=False):
+        """c[r] = sum_j a[r][j] * b[r][j] in Z_q[x]/(x^n+1) with BOTH operands prepared (tn_poly_dot_hat_dev).  a_prepared holds
+        batch * terms rows (the terms of one output row are consecutive); b_prepared holds as many, or `terms` rows that every
+        output row is multiplied by.  Returns a device tensor (batch, n) of coefficients, or, with keep_prepared, a
+        PreparedOperand of batch rows (no transform runs; prepared rows of one plan add word-wise mod q)."""
+        import torch
+        self._own_prepared(a_prepared, "poly_dot_hat", "first operand")
+        self._own_prepared(b_prepared, "poly_dot_hat", "second operand")
+        terms = int(terms)
+        if terms < 1 or a_prepared.rows % terms:
+            raise ValueError(f"Expected a first operand of batch * {terms} rows, got {a_prepared.rows}")
+        batch = a_prepared.rows // terms
+        if b_prepared.rows not in (terms, batch * terms):
+            raise ValueError(f"Expected a second operand of {terms} or {batch * terms} rows, got {b_prepared.rows}")
+        sets = 1 if b_prepared.rows == terms else batch
+        if isinstance(out, PreparedOperand):
+            out = out.tensor
+        c = out if out is not None else torch.empty((batch, self.n), dtype=self.torch_dtype, device=a_prepared.tensor.device)
+        if self._dev_rows(c, "out") != batch:
+            raise ValueError(f"Expected an output of {batch} rows of {self.n} coefficients")
+        _check(self._lib, self._lib.tn_poly_dot_hat_dev(self._h, a_prepared.tensor.data_ptr(), b_prepared.tensor.data_ptr(), sets, c.data_ptr(), batch,
+                                                        terms, 1 if keep_prepared else 0, self._stream_ptr(stream)))
+        return PreparedOperand(self, c, batch) if keep_prepared else c
 
     def cyclic_poly_mult(self, a, b, variant="auto", out=None, stream=None):
         """Untwisted product forward->pointwise->inverse: python_poly_mult (test_ntt_poly_mult.py:38-43)."""
