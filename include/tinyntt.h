@@ -233,6 +233,52 @@ tn_status tn_poly_dot_hat_dev(tn_plan *plan, const void *ahat, const void *bhat,
                               size_t terms, int out_prepared, void *stream);
 
 /*
+ * GADGET decomposition: the base-2^w digits of every coefficient of a, written out (tn_gadget_decompose_dev) or cut inside the
+ * dot-product kernel (tn_poly_gadget_dot_prepared_dev), which is a key switch, a relinearisation or an external product
+ * against a prepared key in ONE launch: a is read once per output row and the digits never exist in memory.
+ *
+ * Definition.  For a word x of a let x^ = x mod q (any word value is accepted), B = 2^w with w = base_log, and
+ * u_j = (x^ >> (j w)) & (B - 1) for j < terms.
+ *   flags == 0 (unsigned):        d_j = u_j.
+ *   TN_GADGET_BALANCED:           carry_0 = 0, t = u_j + carry_j; t >= B/2: d_j = t - B, carry_{j+1} = 1; otherwise d_j = t,
+ *                                 carry_{j+1} = 0.  d_j is in [-B/2, B/2); the last carry is dropped.
+ * A digit is stored and used as its canonical residue d_j mod q (a negative digit as q + d_j).  Digit polynomial j of row r
+ * holds digit j of every coefficient of a[r].  Digits above terms * w bits are not produced: the caller chooses terms.
+ *
+ * tn_gadget_decompose_dev: digits[r][j] = digit polynomial j of a[r]: a is [batch][n], digits is [batch][terms][n] canonical
+ * residues, the layout tn_poly_dot_prepared_dev takes as its a.  An element-wise kernel; works on EVERY plan (general and
+ * omega-only plans included).  digits must not overlap a (TN_EINVAL).
+ *
+ * tn_poly_gadget_dot_prepared_dev: c[r] = sum_{j < terms} digit_j(a[r]) * b[s][j] in Z_q[x]/(x^n+1), s = (bhat_sets == 1 ? 0 : r),
+ * r < batch: a is [batch][n], bhat is [bhat_sets][terms][n] as tn_prepare_dev wrote it, bhat_sets is 1 or batch, c is
+ * [batch][n] canonical residues, BIT-IDENTICAL to tn_poly_dot_prepared_dev on the output of tn_gadget_decompose_dev.
+ * terms == 1 is one digit and the prepared product.
+ *
+ * When to use which (MI355X, profiles/gadget_dot_ab.txt; slowest repeat of the fused call against the fastest of
+ * tn_gadget_decompose_dev followed by tn_poly_dot_prepared_dev on the same buffers, balanced digits, terms 2 - 4):
+ *   - a given undecomposed: tn_poly_gadget_dot_prepared_dev is faster at every measured point, x 0.67 - 0.71 of the two launches at
+ *     n = 4096 / 60-bit, 65,536 rows (4,795 against 6,998 us at four terms, shared set) and x 0.64 - 0.69 at n = 1024 / 24-bit,
+ *     4,096 rows.  No measured point is slower.
+ *   - digits that already exist in memory (decomposed once, used by several launches): tn_poly_dot_prepared_dev on them costs the
+ *     same as the fused call on a (x 0.97 - 1.00 at n = 4096 / 60-bit, x 1.01 - 1.04 at n = 1024 / 24-bit: there the fused call is
+ *     1 - 4 % SLOWER than the dot product alone), so nothing is gained by decomposing again.
+ *   - n = 256 was not measured.
+ *
+ * TN_EINVAL, for both: a NULL plan or buffer, terms == 0, base_log == 0, 2^base_log >= q, (terms - 1) * base_log >= 64 (no
+ * shift reaches the word width), a flag bit other than TN_GADGET_BALANCED, batch * terms > 2^31 - 1, an output overlapping an
+ * input (byte ranges; c against a's batch rows and bhat's bhat_sets * terms rows); bhat_sets neither 1 nor batch.
+ * TN_EUNSUPPORTED: tn_poly_gadget_dot_prepared_dev on a plan without the fused kernels (as tn_poly_dot_prepared_dev).
+ * batch == 0 succeeds and launches nothing.  Both enqueue on the stream and return, and may be stream-captured (a captured
+ * launch hands rows out at the fixed stride).  The negacyclic product only: no cyclic variant, no *_host form and no
+ * tn_multi_* form.  The reference has no counterpart: it has neither a decomposition nor a transform-domain handle.
+ */
+#define TN_GADGET_BALANCED 1u
+tn_status tn_gadget_decompose_dev(tn_plan *plan, const void *a, void *digits, size_t batch, size_t terms, uint32_t base_log,
+                                  uint32_t flags, void *stream);
+tn_status tn_poly_gadget_dot_prepared_dev(tn_plan *plan, const void *a, const void *bhat, size_t bhat_sets, void *c, size_t batch,
+                                          size_t terms, uint32_t base_log, uint32_t flags, void *stream);
+
+/*
  * The *_host entry points cut the batch into chunks that flow H2D -> kernel -> D2H on three
  * streams through a fixed set of device staging slots (copies overlap the kernels when the host
  * buffers are pinned; device staging stays bounded whatever the batch).  rows = rows per chunk,

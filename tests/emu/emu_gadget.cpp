@@ -1,0 +1,140 @@
+// emu_gadget.cpp — TEST INFRASTRUCTURE: steps the gadget dot-product kernel (polydot_gadget_kernel: tiny_ntt_amd/csrc/kernels.hip)
+// on the CPU, one emulated thread at a time, with the Stepper of emu_kernels.cpp, the headers the gfx950 kernel is compiled from,
+// its canonicalise-and-digit functions (fused_core.h: gadget_canon, gadget_digit), its accumulate function (dot_accumulate) and
+// the prepared-order index map (FusedCfg::prep_idx).  Kernel variant, tables and constants come from fused_product_setup
+// (launch_plan.h), as in the launcher.  Built into its own library by tests/emu/Makefile.gadget; loaded by
+// tests/test_gadget_emu.py and tests/test_gpu_gadget.py.
+#include "emu_kernels.cpp"
+
+namespace {
+
+// what tn_gadget_decompose_dev / tn_poly_gadget_dot_prepared_dev refuse (capi.cpp: check_gadget)
+bool gadget_ok(u64 q, size_t terms, u32 base_log, u32 flags) {
+  if (terms == 0 || (flags & ~1u)) return false;
+  if (base_log == 0 || base_log >= 64 || (((u64)1) << base_log) >= q) return false;
+  return terms - 1 <= 63 / base_log;
+}
+
+// Same steps as polydot_gadget_kernel: per output row the words of a are made canonical once (gadget_canon); every term cuts
+// its digit out of them (gadget_digit, the carries of the thread's words in one mask), runs one forward transform WITHOUT
+// load_reduce and the product against its prepared row; the products are summed by dot_accumulate and one inverse runs on the sum.
+template <typename E, int LOGN, int LPT, bool LAZY, bool BC>
+int polydot_gadget_emu(const HostTables& t, const u64* a, const u64* bhat, size_t bhat_sets, u64* c, size_t batch, size_t terms, u32 base_log,
+                       bool balanced) {
+  typedef Policy<E, LAZY> Pol;
+  typedef Stepper<E, LOGN, LPT, Pol, BC> S;
+  typedef typename S::Cfg Cfg;
+  static_assert(Cfg::R <= 32, "one carry bit per word of the thread in a 32-bit mask");
+  const FusedProductSetup<E> su = fused_product_setup(h_make_arith<E>(t), BC, false);
+  S wg{su.ar};
+  const typename S::Table fwd(t, su.fwd), inv(t, su.inv);
+  std::vector<typename S::Regs> xw(S::T), xa(S::T), xb(S::T), acc(S::T);
+  std::vector<u32> carries(S::T);
+  for (size_t row = 0; row < batch; ++row) {
+    for (u32 tau = 0; tau < S::T; ++tau) {
+      for (int r = 0; r < Cfg::R; ++r) {
+        xw[tau].x[r] = gadget_canon<E, Pol>((E)a[(row << LOGN) + Cfg::jidx(0, tau, r)], wg.ar);
+        acc[tau].x[r] = 0;
+      }
+      carries[tau] = 0;
+    }
+    for (size_t j = 0; j < terms; ++j) {
+      const size_t boff = ((bhat_sets == 1 ? 0 : row) * terms + j) << LOGN;
+      const u32 shift = (u32)j * base_log;
+      for (u32 tau = 0; tau < S::T; ++tau) {
+        u32 next_carries = 0;
+        for (int r = 0; r < Cfg::R; ++r) {
+          xb[tau].x[r] = (E)bhat[boff + Cfg::prep_idx(tau, (u32)r)];
+          u32 cy = (carries[tau] >> r) & 1u;
+          xa[tau].x[r] = gadget_digit<E>(xw[tau].x[r], shift, base_log, balanced, cy, wg.ar.q);
+          next_carries |= cy << r;
+        }
+        carries[tau] = next_carries;
+      }
+      wg.forward(xa, fwd);
+      for (u32 tau = 0; tau < S::T; ++tau) {
+        if constexpr (BC) basecase<Cfg, Pol>(xa[tau].x, xb[tau].x, wg.pre[tau].t + Cfg::pre_off(LOGN - 1), wg.ar);   // the zeta records came with the forward's
+        else pointwise<E, Cfg, Pol>(xa[tau].x, xb[tau].x, wg.ar);
+        dot_accumulate<E, Cfg, Pol>(acc[tau].x, xa[tau].x, wg.ar);
+      }
+    }
+    wg.inverse(acc, inv);
+    for (u32 tau = 0; tau < S::T; ++tau)
+      for (int r = 0; r < Cfg::R; ++r) c[(row << LOGN) + Cfg::jidx(0, tau, r)] = acc[tau].x[r];
+  }
+  return 0;
+}
+
+// The base case exactly where the launcher selects it.
+template <typename E, int LOGN, bool LAZY>
+int gadget_shape(const HostTables& t, const u64* a, const u64* bhat, size_t bhat_sets, u64* c, size_t batch, size_t terms, u32 base_log, bool balanced) {
+  constexpr int LPT = fused_lpt(LOGN);
+  if constexpr (fused_has_bc<E, LOGN, LPT, LAZY>()) {
+    if (t.bc_ok) return polydot_gadget_emu<E, LOGN, LPT, LAZY, true>(t, a, bhat, bhat_sets, c, batch, terms, base_log, balanced);
+  }
+  return polydot_gadget_emu<E, LOGN, LPT, LAZY, false>(t, a, bhat, bhat_sets, c, batch, terms, base_log, balanced);
+}
+
+template <typename E, bool LAZY>
+int gadget_dispatch(const HostTables& t, const u64* a, const u64* bhat, size_t bhat_sets, u64* c, size_t batch, size_t terms, u32 base_log, bool balanced) {
+  switch (t.logn) {
+    case 8: return gadget_shape<E, 8, LAZY>(t, a, bhat, bhat_sets, c, batch, terms, base_log, balanced);
+    case 9: return gadget_shape<E, 9, LAZY>(t, a, bhat, bhat_sets, c, batch, terms, base_log, balanced);
+    case 10: return gadget_shape<E, 10, LAZY>(t, a, bhat, bhat_sets, c, batch, terms, base_log, balanced);
+    case 11: return gadget_shape<E, 11, LAZY>(t, a, bhat, bhat_sets, c, batch, terms, base_log, balanced);
+    case 12: return gadget_shape<E, 12, LAZY>(t, a, bhat, bhat_sets, c, batch, terms, base_log, balanced);
+    case 13: return gadget_shape<E, 13, LAZY>(t, a, bhat, bhat_sets, c, batch, terms, base_log, balanced);
+    default: return 7;
+  }
+}
+
+// digits[i * terms + j] = digit j of word x[i]: the kernel's two functions in the kernel's order
+template <typename E, bool LAZY>
+void digit_words(const HostTables& t, const u64* x, u64* digits, size_t count, size_t terms, u32 base_log, bool balanced) {
+  const Arith<E> ar = h_make_arith<E>(t);
+  for (size_t i = 0; i < count; ++i) {
+    const E xc = gadget_canon<E, Policy<E, LAZY>>((E)x[i], ar);
+    u32 carry = 0;
+    for (size_t j = 0; j < terms; ++j) digits[i * terms + j] = gadget_digit<E>(xc, (u32)j * base_log, base_log, balanced, carry, ar.q);
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+// c[r] = sum_j digit_j(a[r]) * b[bhat_sets == 1 ? 0 : r][j].  0 ok, 2 bad params, 3 bad bhat_sets / a, 4 what the gadget calls
+// refuse (terms, base_log, flags), 7 unsupported n.  Coefficients and prepared words travel as uint64 regardless of lane
+// width.  canonical: the canonical policy (TN_PLAN_FORCE_CANONICAL).  flags: bit 0 = balanced digits (TN_GADGET_BALANCED).
+int emu_poly_gadget_dot_prepared(uint32_t n, uint64_t q, uint64_t psi, int canonical, const uint64_t* a, const uint64_t* bhat, size_t bhat_sets,
+                                 uint64_t* c, size_t batch, size_t terms, uint32_t base_log, uint32_t flags) {
+  if (bhat_sets != 1 && bhat_sets != batch) return 3;
+  if (!a) return 3;
+  if (!params_ok(n, q, psi)) return 2;
+  if (!gadget_ok(q, terms, base_log, flags)) return 4;
+  const HostTables t = h_build_tables(n, q, psi, !(canonical & 1));
+  const bool bal = (flags & 1u) != 0;
+  if (t.elem_bytes == 8)
+    return t.lazy ? gadget_dispatch<u64, true>(t, a, bhat, bhat_sets, c, batch, terms, base_log, bal)
+                  : gadget_dispatch<u64, false>(t, a, bhat, bhat_sets, c, batch, terms, base_log, bal);
+  return t.lazy ? gadget_dispatch<u32, true>(t, a, bhat, bhat_sets, c, batch, terms, base_log, bal)
+                : gadget_dispatch<u32, false>(t, a, bhat, bhat_sets, c, batch, terms, base_log, bal);
+}
+
+// digits[i][j] = gadget_digit(gadget_canon(x[i]), j) for j < terms, with the lane width, policy and constants of the plan
+// (n, q, psi, canonical); x[i] is truncated to the lane.  Returns 0, 2 for bad params, 4 for what the gadget calls refuse;
+// *lane_bytes / *lazy tell which instantiation ran.
+int emu_gadget_digits(uint32_t n, uint64_t q, uint64_t psi, int canonical, const uint64_t* x, uint64_t* digits, size_t count, size_t terms,
+                      uint32_t base_log, uint32_t flags, int* lane_bytes, int* lazy) {
+  if (!params_ok(n, q, psi)) return 2;
+  if (!gadget_ok(q, terms, base_log, flags)) return 4;
+  const HostTables t = h_build_tables(n, q, psi, !(canonical & 1));
+  if (lane_bytes) *lane_bytes = t.elem_bytes;
+  if (lazy) *lazy = t.lazy ? 1 : 0;
+  const bool bal = (flags & 1u) != 0;
+  if (t.elem_bytes == 8) { if (t.lazy) digit_words<u64, true>(t, x, digits, count, terms, base_log, bal); else digit_words<u64, false>(t, x, digits, count, terms, base_log, bal); }
+  else { if (t.lazy) digit_words<u32, true>(t, x, digits, count, terms, base_log, bal); else digit_words<u32, false>(t, x, digits, count, terms, base_log, bal); }
+  return 0;
+}
+
+}  // extern "C"

@@ -330,6 +330,53 @@ extern "C" tn_status tn_poly_dot_hat_dev(tn_plan* p, const void* ahat, const voi
   return TN_OK;
 }
 
+// ---- gadget decomposition: digits of a, written out or cut inside the dot-product kernel -----------
+// the conditions both gadget calls share; 0 < base_log, 2^base_log < q, terms >= 1, no shift reaches the word width
+static tn_status check_gadget(const tn_plan* p, size_t batch, size_t terms, uint32_t base_log, uint32_t flags, const char* fn) {
+  if (terms == 0) return fail(TN_EINVAL, std::string(fn) + ": terms must be at least 1");
+  if (flags & ~(uint32_t)TN_GADGET_BALANCED) return fail(TN_EINVAL, std::string(fn) + ": unknown flag bit");
+  if (base_log == 0 || base_log >= 64 || (((u64)1) << base_log) >= p->q) return fail(TN_EINVAL, std::string(fn) + ": need 1 <= base_log and 2^base_log < q");
+  if (terms - 1 > 63 / base_log) return fail(TN_EINVAL, std::string(fn) + ": (terms - 1) * base_log must be below 64");
+  // (rows are indexed with 32 bits; the division keeps batch * terms from wrapping size_t first)
+  if (batch > 0x7fffffffull || (batch && terms > 0x7fffffffull / batch))
+    return fail(TN_EINVAL, std::string(fn) + ": batch * terms too large for one call (max 2^31 - 1 digit rows)");
+  return TN_OK;
+}
+
+extern "C" tn_status tn_gadget_decompose_dev(tn_plan* p, const void* a, void* digits, size_t batch, size_t terms, uint32_t base_log,
+                                             uint32_t flags, void* stream) {
+  const char* fn = "tn_gadget_decompose_dev";
+  if (!p) return fail(TN_EINVAL, std::string(fn) + ": plan is NULL");
+  tn_status st = check_gadget(p, batch, terms, base_log, flags, fn);
+  if (st) return st;
+  if (batch == 0) return TN_OK;
+  if (!a || !digits) return fail(TN_EINVAL, std::string(fn) + ": NULL buffer");
+  const size_t row_bytes = (size_t)p->n * (size_t)p->elem_bytes;
+  if (ranges_overlap(digits, batch * terms * row_bytes, a, batch * row_bytes))
+    return fail(TN_EINVAL, std::string(fn) + ": output must not alias or overlap the input");
+  TN_ON_DEVICE(p);
+  TN_HIP(launch_gadget_decompose(p, a, digits, batch, terms, base_log, (flags & TN_GADGET_BALANCED) != 0, pick_stream(p, stream)));
+  return TN_OK;
+}
+
+extern "C" tn_status tn_poly_gadget_dot_prepared_dev(tn_plan* p, const void* a, const void* bhat, size_t bhat_sets, void* c, size_t batch,
+                                                     size_t terms, uint32_t base_log, uint32_t flags, void* stream) {
+  const char* fn = "tn_poly_gadget_dot_prepared_dev";
+  if (!p) return fail(TN_EINVAL, std::string(fn) + ": plan is NULL");
+  if (!p->has_fused) return fail(TN_EUNSUPPORTED, std::string(fn) + ": prepared operands need a plan with the fused kernels (tn_plan_has_fused)");
+  tn_status st = check_gadget(p, batch, terms, base_log, flags, fn);
+  if (st) return st;
+  if (batch == 0) return TN_OK;
+  if (!a || !bhat || !c) return fail(TN_EINVAL, std::string(fn) + ": NULL buffer");
+  if (bhat_sets != 1 && bhat_sets != batch) return fail(TN_EINVAL, std::string(fn) + ": bhat_sets must be 1 (one set of operands for every row) or batch");
+  const size_t row_bytes = (size_t)p->n * (size_t)p->elem_bytes;
+  if (ranges_overlap(c, batch * row_bytes, a, batch * row_bytes) || ranges_overlap(c, batch * row_bytes, bhat, bhat_sets * terms * row_bytes))
+    return fail(TN_EINVAL, std::string(fn) + ": output must not alias or overlap an input");
+  TN_ON_DEVICE(p);
+  TN_HIP(launch_polydot_gadget(p, a, bhat, bhat_sets == 1, c, batch, terms, base_log, (flags & TN_GADGET_BALANCED) != 0, pick_stream(p, stream)));
+  return TN_OK;
+}
+
 extern "C" tn_status tn_pointwise_mul_dev(tn_plan* p, const void* a, const void* b, void* c, size_t batch, void* stream) {
   if (!p) return fail(TN_EINVAL, "tn_pointwise_mul_dev: plan is NULL");
   if (batch > 0xffffffffull) return fail(TN_EINVAL, "tn_pointwise_mul_dev: batch too large");

@@ -669,4 +669,29 @@ TN_HD void dot_accumulate(E (&acc)[Cfg::R], const E (&x)[Cfg::R], const Arith<E>
   for (int r = 0; r < Cfg::R; ++r) acc[r] = dot_accumulate_one<E, Pol>(acc[r], x[r], ar);
 }
 
+// Gadget decomposition (tn_gadget_decompose_dev, polydot_gadget_kernel: kernels.hip).
+// gadget_canon: ANY word of the lane -> its residue in [0, q), exactly.
+//   lazy: one fold() of any word lands below 2q (h_lazy_ok, plan_tables.h: c (floor(2^W / 2^k) + 1) <= q; replayed for the
+//     split policy as folded(2^64) <= 2q by h_split_sched_replay), so one conditional subtraction finishes.  That is
+//     Pol::canon(Pol::load(x)) with canon's second fold left out: on a value below 2q that fold is the same subtraction.
+//   canonical: mul_tw(x, one, q) = x mod q for any word (mul_tw_lazy is below 4q / 2q for ANY multiplicand; Policy::load).
+template <typename E, typename Pol>
+TN_HD E gadget_canon(E x, const Arith<E>& ar) {
+  if (Pol::lazy) return csub(fold(x, ar.k, ar.fold_c), ar.q);
+  return mul_tw(x, ar.one, ar.q);
+}
+// Digit j of a canonical word x as a canonical residue: u = (x >> j w) mod B, B = 2^w < q, shift = j w < 64; on a 32-bit lane a
+// shift of 32 or more gives 0 (the lane is not widened: a 64-bit shift kept the R words of a as register pairs, 8 registers).
+// Unsigned: u.  Balanced: t = u + carry (0 or 1, the previous digit's; 0 for digit 0); t >= B/2 -> t - B, stored as q + t - B
+// (t == B gives 0; a select, not csub: 6 registers fewer at n = 256 / 64-bit), and a carry into the next digit.
+template <typename E>
+TN_HD E gadget_digit(E x, u32 shift, u32 w, bool balanced, u32& carry, E q) {
+  const E B = (E)1 << w;
+  const E sh = sizeof(E) == 8 ? (E)((u64)x >> shift) : (shift < 32 ? (E)((u32)x >> (shift & 31)) : (E)0);
+  const E t = (E)(sh & (E)(B - 1)) + (E)carry;   // <= B
+  const bool neg = balanced && t >= (E)(B >> 1);
+  carry = neg ? 1u : 0u;
+  return neg ? (t == B ? (E)0 : (E)(t + (E)(q - B))) : t;
+}
+
 }  // namespace tn

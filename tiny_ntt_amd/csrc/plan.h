@@ -190,6 +190,12 @@ hipError_t launch_polydot_prepared(const tn_plan* p, const void* a, const void* 
 hipError_t launch_unprepare(const tn_plan* p, const void* xhat, void* x, size_t rows, hipStream_t s);
 hipError_t launch_polydot_hat(const tn_plan* p, const void* ahat, const void* bhat, bool shared, void* out, size_t batch, size_t terms,
                               bool out_prepared, hipStream_t s);
+// gadget decomposition (tn_gadget_decompose_dev: every plan) and the dot product that decomposes a itself
+// (tn_poly_gadget_dot_prepared_dev: fused plans only): c[r] = sum_j digit_j(a[r]) * b[shared ? 0 : r][j]
+hipError_t launch_gadget_decompose(const tn_plan* p, const void* a, void* digits, size_t batch, size_t terms, tn::u32 base_log, bool balanced,
+                                   hipStream_t s);
+hipError_t launch_polydot_gadget(const tn_plan* p, const void* a, const void* bhat, bool shared, void* c, size_t batch, size_t terms,
+                                 tn::u32 base_log, bool balanced, hipStream_t s);
 hipError_t launch_cg(const tn_plan* p, int mode, int group, int layout, const void* a, const void* b, void* out,
                      void* trace, size_t batch, hipStream_t s);
 hipError_t launch_pointwise(const tn_plan* p, const void* a, const void* b, void* c, size_t batch, hipStream_t s);

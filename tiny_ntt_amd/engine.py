@@ -31,6 +31,7 @@ VARIANTS = {"auto": VARIANT_AUTO, "fused": VARIANT_FUSED, "cg": VARIANT_CG, "cg8
             "cg_swizzled": 5, "cg8_swizzled": 6, "cg2": 7, "cg2_padded": 8, "cg2_swizzled": 9, "cg4": 10, "cg4_padded": 11, "cg4_swizzled": 12}
 CG_VARIANTS = tuple(k for k in VARIANTS if k.startswith("cg"))
 PLAN_FORCE_CANONICAL = 1
+GADGET_BALANCED = 1           # digits in [-B/2, B/2): include/tinyntt.h TN_GADGET_BALANCED
 PLAN_CANONICAL_INPUTS = 2     # the caller promises inputs in [0, q): include/tinyntt.h TN_PLAN_CANONICAL_INPUTS
 
 # Every symbol include/tinyntt.h declares (tests check the built library exports them all).
@@ -39,6 +40,7 @@ EXPORTED_SYMBOLS = (
     "tn_plan_elem_bytes", "tn_plan_device", "tn_plan_has_fused", "tn_plan_is_lazy",
     "tn_poly_mult_dev", "tn_poly_mult_host", "tn_plan_set_host_chunk_rows", "tn_cyclic_poly_mult_dev", "tn_pointwise_mul_dev", "tn_schoolbook_dev",
     "tn_prepare_dev", "tn_poly_mult_prepared_dev", "tn_poly_dot_prepared_dev", "tn_unprepare_dev", "tn_poly_dot_hat_dev",
+    "tn_gadget_decompose_dev", "tn_poly_gadget_dot_prepared_dev",
     "tn_plan_export_table", "tn_ntt_forward_dev", "tn_ntt_inverse_dev",
     "tn_ntt_forward_host", "tn_ntt_inverse_host", "tn_ntt_forward_trace_host", "tn_twisted_ntt_forward_dev",
     "tn_twisted_ntt_forward_host", "tn_schoolbook_host",
@@ -96,6 +98,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.tn_poly_dot_prepared_dev.argtypes = [vp, vp, vp, sz, vp, sz, sz, vp]
     lib.tn_unprepare_dev.argtypes = [vp, vp, vp, sz, vp]
     lib.tn_poly_dot_hat_dev.argtypes = [vp, vp, vp, sz, vp, sz, sz, ci, vp]
+    lib.tn_gadget_decompose_dev.argtypes = [vp, vp, vp, sz, sz, u32, u32, vp]
+    lib.tn_poly_gadget_dot_prepared_dev.argtypes = [vp, vp, vp, sz, vp, sz, sz, u32, u32, vp]
     lib.tn_schoolbook_dev.argtypes = [vp, vp, vp, vp, sz, vp]
     lib.tn_plan_export_table.argtypes = [vp, ci, vp]
     for name in ("tn_ntt_forward_dev", "tn_ntt_inverse_dev", "tn_twisted_ntt_forward_dev"):
@@ -433,6 +437,63 @@ class Plan:
         _check(self._lib, self._lib.tn_poly_dot_hat_dev(self._h, a_prepared.tensor.data_ptr(), b_prepared.tensor.data_ptr(), sets, c.data_ptr(), batch,
                                                         terms, 1 if keep_prepared else 0, self._stream_ptr(stream)))
         return PreparedOperand(self, c, batch) if keep_prepared else c
+
+    def _gadget_rows(self, a):
+        """a as a contiguous device tensor (batch, n) -> (tensor, batch, came from the host, one polynomial)."""
+        host = not _is_torch(a)
+        squeeze = (np.ndim(a) if host else a.dim()) == 1
+        if host:
+            a = self.to_device(a)
+        return a, self._dev_rows(a, "a"), host, squeeze
+
+    def gadget_decompose(self, a, terms, base_log, balanced=False, out=None, stream=None):
+        """The base-2^base_log digits of every coefficient of a, taken mod q (tn_gadget_decompose_dev; include/tinyntt.h has the
+        definition): a is (batch, n) or (n,), host values or a device tensor; returns (batch, terms, n) or (terms, n), canonical
+        residues, digit polynomial j of row r at [r, j].  balanced: digits in [-B/2, B/2), negative ones stored as q + d.  Works
+        on every plan."""
+        import torch
+        a, batch, host, squeeze = self._gadget_rows(a)
+        terms = int(terms)
+        if terms < 1:
+            raise ValueError(f"Expected terms >= 1, got {terms}")
+        d = out if out is not None else torch.empty((batch, terms, self.n), dtype=self.torch_dtype, device=a.device)
+        if not d.is_contiguous() or d.dtype != self.torch_dtype or d.numel() != batch * terms * self.n:
+            raise ValueError(f"Expected an output of {batch} x {terms} rows of {self.n} coefficients")
+        _check(self._lib, self._lib.tn_gadget_decompose_dev(self._h, a.data_ptr(), d.data_ptr(), batch, terms, int(base_log),
+                                                            GADGET_BALANCED if balanced else 0, self._stream_ptr(stream)))
+        if host:
+            res = self.to_host(d.reshape(batch * terms, self.n)).reshape(batch, terms, self.n)
+            return res[0] if squeeze else res
+        if out is None:
+            d = d.reshape(batch, terms, self.n)
+            return d[0] if squeeze else d
+        return d
+
+    def poly_gadget_dot_prepared(self, a, prepared: PreparedOperand, terms, base_log, balanced=False, out=None, stream=None):
+        """c[r] = sum_j digit_j(a[r]) * b[r][j] in Z_q[x]/(x^n+1) with b given as Plan.prepare(b) (tn_poly_gadget_dot_prepared_dev):
+        the digits of gadget_decompose are cut inside the kernel, so a is read once and they never reach memory.  a is (batch, n)
+        or (n,); the prepared operand has batch * terms rows, or `terms` rows that every output row is multiplied by.  Returns
+        (batch, n) or (n,), bit-identical to poly_dot_prepared(gadget_decompose(a, ...), prepared)."""
+        import torch
+        self._own_prepared(prepared, "poly_gadget_dot_prepared", "second operand")
+        a, batch, host, squeeze = self._gadget_rows(a)
+        terms = int(terms)
+        if terms < 1:
+            raise ValueError(f"Expected terms >= 1, got {terms}")
+        if prepared.rows not in (terms, batch * terms):
+            raise ValueError(f"Expected a prepared operand of {terms} or {batch * terms} rows, got {prepared.rows}")
+        sets = 1 if prepared.rows == terms else batch
+        c = out if out is not None else torch.empty((batch, self.n), dtype=self.torch_dtype, device=a.device)
+        if self._dev_rows(c, "out") != batch:
+            raise ValueError(f"Expected an output of {batch} rows of {self.n} coefficients")
+        _check(self._lib, self._lib.tn_poly_gadget_dot_prepared_dev(self._h, a.data_ptr(), prepared.tensor.data_ptr(), sets, c.data_ptr(), batch, terms,
+                                                                    int(base_log), GADGET_BALANCED if balanced else 0, self._stream_ptr(stream)))
+        if host:
+            res = self.to_host(c)
+            return res[0] if squeeze else res
+        if out is None and squeeze:
+            return c[0]
+        return c
 
     def cyclic_poly_mult(self, a, b, variant="auto", out=None, stream=None):
         """Untwisted product forward->pointwise->inverse: python_poly_mult (test_ntt_poly_mult.py:38-43)."""
