@@ -365,7 +365,9 @@ def test_fused_emulation_chosen_spectra_and_boundary_rows(emu, oracle, n, q):
     pairs, seeded picks), their unreduced twins a + j q, and rows with every coefficient at a fold boundary (q, 2q, 2^k, the largest
     multiple of q in the word, ...) times a random row and times themselves (tests/chosen_rows.py): the pointwise product and the
     base case see 0, 1 and q - 1, the load step sees its boundaries.  Every fused shape, both policies, the base-case product where a
-    plan takes it, the standalone transforms of the same rows; expected values from the oracle.
+    plan takes it (among SHAPES that is exactly (4096, 2^60 - 2^14 + 1); tests/policy_moduli.py lists the other base-case moduli
+    and tests/test_policy_moduli_emu.py sends these rows through them), the standalone transforms of the same rows; expected values
+    from the oracle.
     (GPU twin: test_gpu_parity.py::test_chosen_spectra_and_boundary_rows.)"""
     import ctypes
     from chosen_rows import chosen_rows, psi_of

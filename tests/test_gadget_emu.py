@@ -104,7 +104,8 @@ def gadget_pairs(q):
     return [(2, -(-k // 2)), (3, -(-k // 3)), (5, 1), (2, k - 1)]
 
 
-def contract_words(q, w, lane_bits, rng):
+def contract_words(q, w, lane_bits, rng, count=1000):
+    """The words of the digit contract: the edges of the digits, of q and of the lane, then `count` random words of the lane."""
     k, B = q.bit_length(), 1 << w
     full = (1 << lane_bits) - 1
     T = (k - 1) // w                               # digits that fit below 2^(k-1) <= q: the word is its own residue
@@ -113,7 +114,35 @@ def contract_words(q, w, lane_bits, rng):
     assert all_top < q and half_run < q
     words = [0, 1, B // 2 - 1, B // 2, B - 1, B, q - 1, q, q + 1, 2 * q - 1, 1 << k, full, all_top, half_run]
     assert all(0 <= x <= full for x in words)
-    return words + [int(v) for v in rng.integers(0, full, 1000, dtype=np.uint64, endpoint=True)]
+    return words + [int(v) for v in rng.integers(0, full, count, dtype=np.uint64, endpoint=True)]
+
+
+def check_digit_contract(gadget, n, q, psi, canonical, lazy, count=1000):
+    """gadget_canon + gadget_digit of the plan (n, q, psi) against the big-integer definition on contract_words, both modes, and
+    the two sums the definition implies.  lazy: the policy the plan must report.  (tests/test_policy_moduli_emu.py runs this at
+    every modulus of tests/policy_moduli.py.)"""
+    k = q.bit_length()
+    lane_bits = 32 if q < 2 ** 31 else 64
+    rng = np.random.default_rng(q % 1000 + canonical)
+    for w in sorted({1, 2, 7, -(-k // 2), k - 1}):
+        B = 1 << w
+        words = contract_words(q, w, lane_bits, rng, count)
+        cover = -(-k // w)                         # terms * w >= k
+        for terms in sorted({1, 3, (k - 1) // w, cover}):
+            if terms < 1 or (terms - 1) * w >= 64:
+                continue
+            for balanced in MODES:
+                out, lane, got_lazy = gadget.digits(n, q, psi, words, terms, w, balanced, canonical)
+                assert lane * 8 == lane_bits and got_lazy == lazy
+                for x, got in zip(words, out):
+                    d, carry = digits_of_word(x, q, w, terms, balanced)
+                    assert [int(v) for v in got] == [v % q for v in d], (n, q, canonical, w, terms, balanced, x)
+                    assert all(-(B // 2) <= v < B // 2 for v in d) if balanced else all(0 <= v < B for v in d)
+                    total = sum(v << (j * w) for j, v in enumerate(d))
+                    if balanced:
+                        assert total == (x % q) % B ** terms - carry * B ** terms
+                    elif terms * w >= k:
+                        assert total == x % q
 
 
 @pytest.mark.parametrize("case", ["P4096_60", "P1024"])
@@ -123,27 +152,7 @@ def test_digit_contract(gadget, case, canonical):
     and canonical policy), both modes, and the two sums the definition implies."""
     n, q, psi = PARAMS[case]
     k = q.bit_length()
-    lane_bits = 64 if q > 2 ** 32 else 32
-    rng = np.random.default_rng(q % 1000 + canonical)
-    for w in sorted({1, 2, 7, -(-k // 2), k - 1}):
-        B = 1 << w
-        words = contract_words(q, w, lane_bits, rng)
-        cover = -(-k // w)                         # terms * w >= k
-        for terms in sorted({1, 3, (k - 1) // w, cover}):
-            if terms < 1 or (terms - 1) * w >= 64:
-                continue
-            for balanced in MODES:
-                out, lane, lazy = gadget.digits(n, q, psi, words, terms, w, balanced, canonical)
-                assert lane * 8 == lane_bits and lazy == (not canonical)
-                for x, got in zip(words, out):
-                    d, carry = digits_of_word(x, q, w, terms, balanced)
-                    assert [int(v) for v in got] == [v % q for v in d], (case, canonical, w, terms, balanced, x)
-                    assert all(-(B // 2) <= v < B // 2 for v in d) if balanced else all(0 <= v < B for v in d)
-                    total = sum(v << (j * w) for j, v in enumerate(d))
-                    if balanced:
-                        assert total == (x % q) % B ** terms - carry * B ** terms
-                    elif terms * w >= k:
-                        assert total == x % q
+    check_digit_contract(gadget, n, q, psi, canonical, not canonical)
     # the carry does run through every digit of those two words
     w = 7
     T = (k - 1) // w

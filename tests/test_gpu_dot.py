@@ -34,9 +34,9 @@ def device_sum(plan, a3, b3):
         p = plan.poly_mult(a3[:, j].contiguous(), b3[:, j].contiguous(), variant="fused")
         if acc is None:
             acc = p
-        else:                                   # canonical words, q < 2^63 / 2^31: the sum fits the signed lane
-            acc = acc + p
-            acc = torch.where(acc >= plan.q, acc - plan.q, acc)
+        else:                                   # canonical words: the sum is below 2q < 2^63 / 2^32; in a 32-bit lane it shows as
+            acc = acc + p                       # negative from 2^31 on (q > 2^30), which is above q, and - q wraps it back
+            acc = torch.where((acc < 0) | (acc >= plan.q), acc - plan.q, acc)
     return acc
 
 

@@ -30,10 +30,11 @@ def hat():
 
 
 def add_mod(plan, x, y):
-    """Word-wise sum mod q of canonical device words (q < 2^63 / 2^31: the sum fits the signed lane)."""
+    """Word-wise sum mod q of canonical device words: below 2q < 2^63 / 2^32; a sum from 2^31 on shows as negative in a 32-bit
+    lane (q > 2^30), is above q, and - q wraps it back."""
     import torch
     s = x + y
-    return torch.where(s >= plan.q, s - plan.q, s)
+    return torch.where((s < 0) | (s >= plan.q), s - plan.q, s)
 
 
 def rows_of(eng, plan, prepared, first, count):

@@ -140,11 +140,13 @@ def test_prepared_words_are_canonical_and_depend_on_b_mod_q_only(prep, case, can
 @pytest.mark.parametrize("case", CASES, ids=CASE_IDS)
 @pytest.mark.parametrize("canonical", [False, True], ids=["lazy", "canonical"])
 def test_prepared_row_is_the_complete_transform_where_no_base_case_runs(prep, emu, case, canonical):
-    """Content independent of layout: without the base case a prepared row is a permutation of twist + forward transform."""
+    """Content independent of layout: without the base case a prepared row is a permutation of twist + forward transform.
+    Among CASES exactly one plan takes the base case; tests/policy_moduli.py lists more (n = 4096, 50 to 60 bits) and
+    tests/test_policy_moduli_emu.py runs them."""
     n, q, psi, a, b = _case_data(case)
     emu.lib.bc_enabled.argtypes = [ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64]
     bc_plan = emu.lib.bc_enabled(n, q, psi) == 1
-    assert bc_plan == (case == "P4096_60")              # the base-case path is exercised by the parity tests: exactly this plan
+    assert bc_plan == (case == "P4096_60")              # among CASES the base-case path is taken by exactly this plan
     bhat = prep.prepare(n, q, psi, b, canonical)
     complete = [np.sort(emu.fused_ntt(n, q, psi, 0, b[r], canonical)) for r in range(b.shape[0])]
     if bc_plan and not canonical:                       # (a canonical-policy plan never runs the base case)
