@@ -1,4 +1,4 @@
-// emu_dot.cpp — TEST INFRASTRUCTURE: steps the prepared dot-product kernel (polydot_prepared_kernel: tiny_ntt_amd/csrc/kernels.hip)
+// emu_dot.cpp — TEST INFRASTRUCTURE: steps the prepared dot-product kernel (polydot_prepared_kernel: tiny_ntt_amd/csrc/kernels_prepared.hip)
 // on the CPU, one emulated thread at a time, with the Stepper of emu_kernels.cpp, the headers the gfx950 kernel is compiled from,
 // its accumulate function (fused_core.h: dot_accumulate) and the prepared-order index map (FusedCfg::prep_idx).  Kernel variant,
 // tables and constants come from fused_product_setup (launch_plan.h), as in the launcher.  Built into its own library by

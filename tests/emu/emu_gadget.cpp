@@ -1,4 +1,4 @@
-// emu_gadget.cpp — TEST INFRASTRUCTURE: steps the gadget dot-product kernel (polydot_gadget_kernel: tiny_ntt_amd/csrc/kernels.hip)
+// emu_gadget.cpp — TEST INFRASTRUCTURE: steps the gadget dot-product kernel (polydot_gadget_kernel: tiny_ntt_amd/csrc/kernels_gadget.hip)
 // on the CPU, one emulated thread at a time, with the Stepper of emu_kernels.cpp, the headers the gfx950 kernel is compiled from,
 // its canonicalise-and-digit functions (fused_core.h: gadget_canon, gadget_digit), its accumulate function (dot_accumulate) and
 // the prepared-order index map (FusedCfg::prep_idx).  Kernel variant, tables and constants come from fused_product_setup

@@ -1,5 +1,5 @@
 // emu_hat.cpp — TEST INFRASTRUCTURE: steps the transform-domain kernels (unprepare_fused_kernel, polydot_hat_kernel:
-// tiny_ntt_amd/csrc/kernels.hip) on the CPU, one emulated thread at a time, with the Stepper of emu_kernels.cpp, the headers the
+// tiny_ntt_amd/csrc/kernels_hat.hip) on the CPU, one emulated thread at a time, with the Stepper of emu_kernels.cpp, the headers the
 // gfx950 kernels are compiled from, their product and accumulate functions (fused_core.h: pointwise, basecase_each,
 // dot_accumulate) and the prepared-order index map (FusedCfg::prep_idx).  Kernel variant, tables and constants come from
 // fused_product_setup (launch_plan.h), as in the launcher.  Built into its own library by tests/emu/Makefile.hat; loaded by

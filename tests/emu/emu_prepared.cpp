@@ -1,5 +1,5 @@
 // emu_prepared.cpp — TEST INFRASTRUCTURE: steps the prepared-operand kernels (prepare_fused_kernel, polymul_prepared_kernel:
-// tiny_ntt_amd/csrc/kernels.hip) on the CPU, one emulated thread at a time, with the Stepper of emu_kernels.cpp, the headers
+// tiny_ntt_amd/csrc/kernels_prepared.hip) on the CPU, one emulated thread at a time, with the Stepper of emu_kernels.cpp, the headers
 // the gfx950 kernels are compiled from and the prepared-order index map the kernels use (FusedCfg::prep_idx).  Kernel
 // variant, tables and constants come from fused_product_setup (launch_plan.h), as in the launchers.  Built into its own
 // library by tests/emu/Makefile.prepared; loaded by tests/test_prepared_emu.py and tests/test_gpu_prepared.py.

@@ -179,7 +179,7 @@ extern "C" int tn_plan_is_general(const tn_plan* p) { return p && p->general && 
 
 static hipStream_t pick_stream(tn_plan* p, void* stream) { return stream ? (hipStream_t)stream : p->stream; }
 
-struct CgSel { int group; int layout; };     // layout: kernels.hip CgLayout (0 linear, 1 padded, 2 swizzled)
+struct CgSel { int group; int layout; };     // layout: CgLayout, cg_core.h (0 linear, 1 padded, 2 swizzled)
 static bool cg_sel(tn_variant v, CgSel* s) {
   switch (v) {
     case TN_VARIANT_CG: *s = {1, 0}; return true;

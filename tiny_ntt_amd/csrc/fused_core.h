@@ -116,7 +116,7 @@ template <typename E, int LOGN_, int LPT_> struct FusedCfg {
   TN_HD static constexpr u32 jidx(int p, u32 tau, u32 r) {
     return ((tau >> pos(p)) << (pos(p) + LPT)) | (r << pos(p)) | (tau & ((1u << pos(p)) - 1u));
   }
-  // Prepared operand (prepare_fused_kernel -> polymul_prepared_kernel, kernels.hip): where register r of thread tau of the LAST
+  // Prepared operand (prepare_fused_kernel -> polymul_prepared_kernel, kernels_prepared.hip): where register r of thread tau of the LAST
   // phase lies within a prepared row.  Register-major, so that each of a thread's R accesses is a unit-stride access of the
   // wave (the addressing of an operand row: ld_operand), and additive in (tau, r): prep_idx(tau, r) == prep_idx(tau, 0) + prep_idx(0, r).
   TN_HD static constexpr u32 prep_idx(u32 tau, u32 r) { return (r << (LOGN - LPT)) | tau; }
@@ -654,7 +654,7 @@ TN_HD void basecase_each(u64 (&xa)[Cfg::R], const u64 (&xb)[Cfg::R], const Tw64*
   });
 }
 
-// Sum of products (polydot_prepared_kernel, kernels.hip): acc += x mod q, term by term, as canonical residues.
+// Sum of products (polydot_prepared_kernel, kernels_prepared.hip): acc += x mod q, term by term, as canonical residues.
 // Precondition: acc in [0, q); x is what the plan's pointwise() / basecase() returns (below PW q, ~9.75 * 2^k after the base
 // case; canonical under the canonical policy): anything Pol::canon accepts.  Postcondition: acc in [0, q), == acc + x (mod q).
 // A canonical word is below every bound the inverse schedules start from (PW q, q, the base case's), and the schedules are
@@ -669,7 +669,7 @@ TN_HD void dot_accumulate(E (&acc)[Cfg::R], const E (&x)[Cfg::R], const Arith<E>
   for (int r = 0; r < Cfg::R; ++r) acc[r] = dot_accumulate_one<E, Pol>(acc[r], x[r], ar);
 }
 
-// Gadget decomposition (tn_gadget_decompose_dev, polydot_gadget_kernel: kernels.hip).
+// Gadget decomposition (tn_gadget_decompose_dev, polydot_gadget_kernel: kernels_gadget.hip).
 // gadget_canon: ANY word of the lane -> its residue in [0, q), exactly.
 //   lazy: one fold() of any word lands below 2q (h_lazy_ok, plan_tables.h: c (floor(2^W / 2^k) + 1) <= q; replayed for the
 //     split policy as folded(2^64) <= 2q by h_split_sched_replay), so one conditional subtraction finishes.  That is

@@ -1,6 +1,6 @@
 // launch_plan.h — what a launch of the persistent kernels decides on the host, as plain functions without the HIP runtime:
 // which fused kernel variant, tables and constants (fused_product_setup, fused_ntt_setup) and how rows are handed out
-// (plan_rows).  The launchers (kernels.hip, cg_kernel_impl.h through plan.h: launch_persistent) and the CPU stepping of
+// (plan_rows).  The launchers (kernels*.hip, cg_kernel_impl.h through plan.h: launch_persistent) and the CPU stepping of
 // tests/emu both take their decisions from here, so the CPU tests check what the launchers do.
 #pragma once
 #include <stddef.h>

@@ -1,5 +1,5 @@
 // plan.h — internal plan object behind the opaque tn_plan handle, the one launch path of the
-// persistent kernels (launch_persistent) and the kernel launch entry points implemented in kernels.hip.
+// persistent kernels (launch_persistent) and the kernel launch entry points implemented in the kernels*.hip files.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -174,7 +174,7 @@ inline hipError_t launch_persistent(const tn_plan* p, hipStream_t s, const void*
   return le;
 }
 
-// kernels.hip
+// kernels.hip (prepared operand: kernels_prepared.hip; transform domain: kernels_hat.hip; gadget: kernels_gadget.hip)
 bool fused_supported(u32 logn, int elem_bytes);
 const char* fused_kernel_name(const tn_plan* p);
 const char* cg_kernel_name(const tn_plan* p, int group, int layout);
