@@ -1,18 +1,20 @@
 // emu_dot.cpp — TEST INFRASTRUCTURE: steps the prepared dot-product kernel (polydot_prepared_kernel: tiny_ntt_amd/csrc/kernels_prepared.hip)
-// on the CPU, one emulated thread at a time, with the Stepper of emu_kernels.cpp, the headers the gfx950 kernel is compiled from,
-// its accumulate function (fused_core.h: dot_accumulate) and the prepared-order index map (FusedCfg::prep_idx).  Kernel variant,
-// tables and constants come from fused_product_setup (launch_plan.h), as in the launcher.  Built into its own library by
-// tests/emu/Makefile.dot; loaded by tests/test_dot_emu.py and tests/test_gpu_dot.py.
-#include "emu_kernels.cpp"
+// on the CPU, one emulated thread at a time, with the Stepper of emu_stepper.h, the headers the gfx950 kernel is compiled from,
+// its accumulate function (fused_core.h: dot_accumulate) and the prepared-order index map (FusedCfg::prep_idx).  Shape and base
+// case come from emu_with_shape, tables and constants from fused_product_setup (launch_plan.h), as in the launcher.  Part of
+// tests/emu/_build/libemu.so; used by tests/test_dot_emu.py and tests/test_gpu_dot.py.
+#include "emu_stepper.h"
 
 namespace {
 
 // Same steps as polydot_prepared_kernel: per output row, every term runs load_reduce, one forward transform and the product
 // against its prepared row, the products are summed by dot_accumulate and one inverse transform runs on the sum.
-template <typename E, int LOGN, int LPT, bool LAZY, bool BC>
+template <typename Sh, bool BC>
 int polydot_prepared_emu(const HostTables& t, const u64* a, const u64* bhat, size_t bhat_sets, u64* c, size_t batch, size_t terms) {
-  typedef Policy<E, LAZY> Pol;
-  typedef Stepper<E, LOGN, LPT, Pol, BC> S;
+  typedef typename Sh::E E;
+  constexpr int LOGN = Sh::LOGN;
+  typedef Policy<E, Sh::LAZY> Pol;
+  typedef Stepper<E, LOGN, Sh::LPT, Pol, BC> S;
   typedef typename S::Cfg Cfg;
   const FusedProductSetup<E> su = fused_product_setup(h_make_arith<E>(t), BC, false);
   S wg{su.ar};
@@ -42,29 +44,6 @@ int polydot_prepared_emu(const HostTables& t, const u64* a, const u64* bhat, siz
   return 0;
 }
 
-// The base case exactly where the launcher selects it.
-template <typename E, int LOGN, bool LAZY>
-int dot_shape(const HostTables& t, const u64* a, const u64* bhat, size_t bhat_sets, u64* c, size_t batch, size_t terms) {
-  constexpr int LPT = fused_lpt(LOGN);
-  if constexpr (fused_has_bc<E, LOGN, LPT, LAZY>()) {
-    if (t.bc_ok) return polydot_prepared_emu<E, LOGN, LPT, LAZY, true>(t, a, bhat, bhat_sets, c, batch, terms);
-  }
-  return polydot_prepared_emu<E, LOGN, LPT, LAZY, false>(t, a, bhat, bhat_sets, c, batch, terms);
-}
-
-template <typename E, bool LAZY>
-int dot_dispatch(const HostTables& t, const u64* a, const u64* bhat, size_t bhat_sets, u64* c, size_t batch, size_t terms) {
-  switch (t.logn) {
-    case 8: return dot_shape<E, 8, LAZY>(t, a, bhat, bhat_sets, c, batch, terms);
-    case 9: return dot_shape<E, 9, LAZY>(t, a, bhat, bhat_sets, c, batch, terms);
-    case 10: return dot_shape<E, 10, LAZY>(t, a, bhat, bhat_sets, c, batch, terms);
-    case 11: return dot_shape<E, 11, LAZY>(t, a, bhat, bhat_sets, c, batch, terms);
-    case 12: return dot_shape<E, 12, LAZY>(t, a, bhat, bhat_sets, c, batch, terms);
-    case 13: return dot_shape<E, 13, LAZY>(t, a, bhat, bhat_sets, c, batch, terms);
-    default: return 7;
-  }
-}
-
 template <typename E, bool LAZY>
 void accumulate_words(const HostTables& t, const u64* acc, const u64* x, u64* out, size_t count) {
   const Arith<E> ar = h_make_arith<E>(t);
@@ -84,8 +63,7 @@ int emu_poly_dot_prepared(uint32_t n, uint64_t q, uint64_t psi, int canonical, c
   if (!a || terms == 0) return 3;
   if (!params_ok(n, q, psi)) return 2;
   const HostTables t = h_build_tables(n, q, psi, !(canonical & 1));
-  if (t.elem_bytes == 8) return t.lazy ? dot_dispatch<u64, true>(t, a, bhat, bhat_sets, c, batch, terms) : dot_dispatch<u64, false>(t, a, bhat, bhat_sets, c, batch, terms);
-  return t.lazy ? dot_dispatch<u32, true>(t, a, bhat, bhat_sets, c, batch, terms) : dot_dispatch<u32, false>(t, a, bhat, bhat_sets, c, batch, terms);
+  return emu_with_shape(t, [&](auto sh, auto bc) { return polydot_prepared_emu<decltype(sh), decltype(bc)::value>(t, a, bhat, bhat_sets, c, batch, terms); });
 }
 
 // out[i] = dot_accumulate_one(acc[i], x[i]) with the lane width, policy and constants of the plan (n, q, psi, canonical).
@@ -96,9 +74,7 @@ int emu_dot_accumulate(uint32_t n, uint64_t q, uint64_t psi, int canonical, cons
   const HostTables t = h_build_tables(n, q, psi, !(canonical & 1));
   if (lane_bytes) *lane_bytes = t.elem_bytes;
   if (lazy) *lazy = t.lazy ? 1 : 0;
-  if (t.elem_bytes == 8) { if (t.lazy) accumulate_words<u64, true>(t, acc, x, out, count); else accumulate_words<u64, false>(t, acc, x, out, count); }
-  else { if (t.lazy) accumulate_words<u32, true>(t, acc, x, out, count); else accumulate_words<u32, false>(t, acc, x, out, count); }
-  return 0;
+  return with_lane_policy(t.elem_bytes, t.lazy, [&](auto e, auto lz) { accumulate_words<decltype(e), decltype(lz)::value>(t, acc, x, out, count); return 0; });
 }
 
 }  // extern "C"

@@ -1,10 +1,10 @@
 // emu_gadget.cpp — TEST INFRASTRUCTURE: steps the gadget dot-product kernel (polydot_gadget_kernel: tiny_ntt_amd/csrc/kernels_gadget.hip)
-// on the CPU, one emulated thread at a time, with the Stepper of emu_kernels.cpp, the headers the gfx950 kernel is compiled from,
+// on the CPU, one emulated thread at a time, with the Stepper of emu_stepper.h, the headers the gfx950 kernel is compiled from,
 // its canonicalise-and-digit functions (fused_core.h: gadget_canon, gadget_digit), its accumulate function (dot_accumulate) and
-// the prepared-order index map (FusedCfg::prep_idx).  Kernel variant, tables and constants come from fused_product_setup
-// (launch_plan.h), as in the launcher.  Built into its own library by tests/emu/Makefile.gadget; loaded by
+// the prepared-order index map (FusedCfg::prep_idx).  Shape and base case come from emu_with_shape, tables and constants from
+// fused_product_setup (launch_plan.h), as in the launcher.  Part of tests/emu/_build/libemu.so; used by
 // tests/test_gadget_emu.py and tests/test_gpu_gadget.py.
-#include "emu_kernels.cpp"
+#include "emu_stepper.h"
 
 namespace {
 
@@ -18,11 +18,13 @@ bool gadget_ok(u64 q, size_t terms, u32 base_log, u32 flags) {
 // Same steps as polydot_gadget_kernel: per output row the words of a are made canonical once (gadget_canon); every term cuts
 // its digit out of them (gadget_digit, the carries of the thread's words in one mask), runs one forward transform WITHOUT
 // load_reduce and the product against its prepared row; the products are summed by dot_accumulate and one inverse runs on the sum.
-template <typename E, int LOGN, int LPT, bool LAZY, bool BC>
+template <typename Sh, bool BC>
 int polydot_gadget_emu(const HostTables& t, const u64* a, const u64* bhat, size_t bhat_sets, u64* c, size_t batch, size_t terms, u32 base_log,
                        bool balanced) {
-  typedef Policy<E, LAZY> Pol;
-  typedef Stepper<E, LOGN, LPT, Pol, BC> S;
+  typedef typename Sh::E E;
+  constexpr int LOGN = Sh::LOGN;
+  typedef Policy<E, Sh::LAZY> Pol;
+  typedef Stepper<E, LOGN, Sh::LPT, Pol, BC> S;
   typedef typename S::Cfg Cfg;
   static_assert(Cfg::R <= 32, "one carry bit per word of the thread in a 32-bit mask");
   const FusedProductSetup<E> su = fused_product_setup(h_make_arith<E>(t), BC, false);
@@ -65,29 +67,6 @@ int polydot_gadget_emu(const HostTables& t, const u64* a, const u64* bhat, size_
   return 0;
 }
 
-// The base case exactly where the launcher selects it.
-template <typename E, int LOGN, bool LAZY>
-int gadget_shape(const HostTables& t, const u64* a, const u64* bhat, size_t bhat_sets, u64* c, size_t batch, size_t terms, u32 base_log, bool balanced) {
-  constexpr int LPT = fused_lpt(LOGN);
-  if constexpr (fused_has_bc<E, LOGN, LPT, LAZY>()) {
-    if (t.bc_ok) return polydot_gadget_emu<E, LOGN, LPT, LAZY, true>(t, a, bhat, bhat_sets, c, batch, terms, base_log, balanced);
-  }
-  return polydot_gadget_emu<E, LOGN, LPT, LAZY, false>(t, a, bhat, bhat_sets, c, batch, terms, base_log, balanced);
-}
-
-template <typename E, bool LAZY>
-int gadget_dispatch(const HostTables& t, const u64* a, const u64* bhat, size_t bhat_sets, u64* c, size_t batch, size_t terms, u32 base_log, bool balanced) {
-  switch (t.logn) {
-    case 8: return gadget_shape<E, 8, LAZY>(t, a, bhat, bhat_sets, c, batch, terms, base_log, balanced);
-    case 9: return gadget_shape<E, 9, LAZY>(t, a, bhat, bhat_sets, c, batch, terms, base_log, balanced);
-    case 10: return gadget_shape<E, 10, LAZY>(t, a, bhat, bhat_sets, c, batch, terms, base_log, balanced);
-    case 11: return gadget_shape<E, 11, LAZY>(t, a, bhat, bhat_sets, c, batch, terms, base_log, balanced);
-    case 12: return gadget_shape<E, 12, LAZY>(t, a, bhat, bhat_sets, c, batch, terms, base_log, balanced);
-    case 13: return gadget_shape<E, 13, LAZY>(t, a, bhat, bhat_sets, c, batch, terms, base_log, balanced);
-    default: return 7;
-  }
-}
-
 // digits[i * terms + j] = digit j of word x[i]: the kernel's two functions in the kernel's order
 template <typename E, bool LAZY>
 void digit_words(const HostTables& t, const u64* x, u64* digits, size_t count, size_t terms, u32 base_log, bool balanced) {
@@ -114,11 +93,9 @@ int emu_poly_gadget_dot_prepared(uint32_t n, uint64_t q, uint64_t psi, int canon
   if (!gadget_ok(q, terms, base_log, flags)) return 4;
   const HostTables t = h_build_tables(n, q, psi, !(canonical & 1));
   const bool bal = (flags & 1u) != 0;
-  if (t.elem_bytes == 8)
-    return t.lazy ? gadget_dispatch<u64, true>(t, a, bhat, bhat_sets, c, batch, terms, base_log, bal)
-                  : gadget_dispatch<u64, false>(t, a, bhat, bhat_sets, c, batch, terms, base_log, bal);
-  return t.lazy ? gadget_dispatch<u32, true>(t, a, bhat, bhat_sets, c, batch, terms, base_log, bal)
-                : gadget_dispatch<u32, false>(t, a, bhat, bhat_sets, c, batch, terms, base_log, bal);
+  return emu_with_shape(t, [&](auto sh, auto bc) {
+    return polydot_gadget_emu<decltype(sh), decltype(bc)::value>(t, a, bhat, bhat_sets, c, batch, terms, base_log, bal);
+  });
 }
 
 // digits[i][j] = gadget_digit(gadget_canon(x[i]), j) for j < terms, with the lane width, policy and constants of the plan
@@ -132,9 +109,7 @@ int emu_gadget_digits(uint32_t n, uint64_t q, uint64_t psi, int canonical, const
   if (lane_bytes) *lane_bytes = t.elem_bytes;
   if (lazy) *lazy = t.lazy ? 1 : 0;
   const bool bal = (flags & 1u) != 0;
-  if (t.elem_bytes == 8) { if (t.lazy) digit_words<u64, true>(t, x, digits, count, terms, base_log, bal); else digit_words<u64, false>(t, x, digits, count, terms, base_log, bal); }
-  else { if (t.lazy) digit_words<u32, true>(t, x, digits, count, terms, base_log, bal); else digit_words<u32, false>(t, x, digits, count, terms, base_log, bal); }
-  return 0;
+  return with_lane_policy(t.elem_bytes, t.lazy, [&](auto e, auto lz) { digit_words<decltype(e), decltype(lz)::value>(t, x, digits, count, terms, base_log, bal); return 0; });
 }
 
 }  // extern "C"

@@ -1,18 +1,20 @@
 // emu_hat.cpp — TEST INFRASTRUCTURE: steps the transform-domain kernels (unprepare_fused_kernel, polydot_hat_kernel:
-// tiny_ntt_amd/csrc/kernels_hat.hip) on the CPU, one emulated thread at a time, with the Stepper of emu_kernels.cpp, the headers the
+// tiny_ntt_amd/csrc/kernels_hat.hip) on the CPU, one emulated thread at a time, with the Stepper of emu_stepper.h, the headers the
 // gfx950 kernels are compiled from, their product and accumulate functions (fused_core.h: pointwise, basecase_each,
-// dot_accumulate) and the prepared-order index map (FusedCfg::prep_idx).  Kernel variant, tables and constants come from
-// fused_product_setup (launch_plan.h), as in the launcher.  Built into its own library by tests/emu/Makefile.hat; loaded by
+// dot_accumulate) and the prepared-order index map (FusedCfg::prep_idx).  Shape and base case come from emu_with_shape, tables
+// and constants from fused_product_setup (launch_plan.h), as in the launcher.  Part of tests/emu/_build/libemu.so; used by
 // tests/test_hat_emu.py and tests/test_gpu_hat.py.
-#include "emu_kernels.cpp"
+#include "emu_stepper.h"
 
 namespace {
 
 // Same steps as unprepare_fused_kernel: the R words at prep_idx are the last phase's registers; the inverse runs on them.
-template <typename E, int LOGN, int LPT, bool LAZY, bool BC>
+template <typename Sh, bool BC>
 int unprepare_emu(const HostTables& t, const u64* xhat, u64* x, size_t rows) {
-  typedef Policy<E, LAZY> Pol;
-  typedef Stepper<E, LOGN, LPT, Pol, BC> S;
+  typedef typename Sh::E E;
+  constexpr int LOGN = Sh::LOGN;
+  typedef Policy<E, Sh::LAZY> Pol;
+  typedef Stepper<E, LOGN, Sh::LPT, Pol, BC> S;
   typedef typename S::Cfg Cfg;
   const FusedProductSetup<E> su = fused_product_setup(h_make_arith<E>(t), BC, false);
   S wg{su.ar};
@@ -32,10 +34,12 @@ int unprepare_emu(const HostTables& t, const u64* xhat, u64* x, size_t rows) {
 // Same steps as polydot_hat_kernel: per output row, every term loads its two prepared rows and runs the product, the products
 // are summed as canonical residues; then one inverse transform and a natural-order store, or (out_prepared) the sum stored at
 // prep_idx.  The zeta records of the base case are fetched once, from stage LOGN - 1 of the forward table, as in the kernel.
-template <typename E, int LOGN, int LPT, bool LAZY, bool BC>
+template <typename Sh, bool BC>
 int polydot_hat_emu(const HostTables& t, const u64* ahat, const u64* bhat, size_t bhat_sets, u64* out, size_t batch, size_t terms, bool out_prepared) {
-  typedef Policy<E, LAZY> Pol;
-  typedef Stepper<E, LOGN, LPT, Pol, BC> S;
+  typedef typename Sh::E E;
+  constexpr int LOGN = Sh::LOGN;
+  typedef Policy<E, Sh::LAZY> Pol;
+  typedef Stepper<E, LOGN, Sh::LPT, Pol, BC> S;
   typedef typename S::Cfg Cfg;
   typedef typename S::Tw Tw;
   const FusedProductSetup<E> su = fused_product_setup(h_make_arith<E>(t), BC, false);
@@ -86,37 +90,16 @@ int polydot_hat_emu(const HostTables& t, const u64* ahat, const u64* bhat, size_
   return 0;
 }
 
-// bhat == nullptr: unprepare.  The base case exactly where the launcher selects it.
-template <typename E, int LOGN, bool LAZY>
-int hat_shape(const HostTables& t, const u64* in, const u64* bhat, size_t bhat_sets, u64* out, size_t batch, size_t terms, bool out_prepared) {
-  constexpr int LPT = fused_lpt(LOGN);
-  if constexpr (fused_has_bc<E, LOGN, LPT, LAZY>()) {
-    if (t.bc_ok)
-      return bhat ? polydot_hat_emu<E, LOGN, LPT, LAZY, true>(t, in, bhat, bhat_sets, out, batch, terms, out_prepared) : unprepare_emu<E, LOGN, LPT, LAZY, true>(t, in, out, batch);
-  }
-  return bhat ? polydot_hat_emu<E, LOGN, LPT, LAZY, false>(t, in, bhat, bhat_sets, out, batch, terms, out_prepared) : unprepare_emu<E, LOGN, LPT, LAZY, false>(t, in, out, batch);
-}
-
-template <typename E, bool LAZY>
-int hat_dispatch(const HostTables& t, const u64* in, const u64* bhat, size_t bhat_sets, u64* out, size_t batch, size_t terms, bool out_prepared) {
-  switch (t.logn) {
-    case 8: return hat_shape<E, 8, LAZY>(t, in, bhat, bhat_sets, out, batch, terms, out_prepared);
-    case 9: return hat_shape<E, 9, LAZY>(t, in, bhat, bhat_sets, out, batch, terms, out_prepared);
-    case 10: return hat_shape<E, 10, LAZY>(t, in, bhat, bhat_sets, out, batch, terms, out_prepared);
-    case 11: return hat_shape<E, 11, LAZY>(t, in, bhat, bhat_sets, out, batch, terms, out_prepared);
-    case 12: return hat_shape<E, 12, LAZY>(t, in, bhat, bhat_sets, out, batch, terms, out_prepared);
-    case 13: return hat_shape<E, 13, LAZY>(t, in, bhat, bhat_sets, out, batch, terms, out_prepared);
-    default: return 7;
-  }
-}
-
+// bhat == nullptr: unprepare.
 int hat_any(uint32_t n, uint64_t q, uint64_t psi, int canonical, const u64* in, const u64* bhat, size_t bhat_sets, u64* out, size_t batch, size_t terms,
             bool out_prepared) {
   if (!params_ok(n, q, psi)) return 2;
   const HostTables t = h_build_tables(n, q, psi, !(canonical & 1));
-  if (t.elem_bytes == 8)
-    return t.lazy ? hat_dispatch<u64, true>(t, in, bhat, bhat_sets, out, batch, terms, out_prepared) : hat_dispatch<u64, false>(t, in, bhat, bhat_sets, out, batch, terms, out_prepared);
-  return t.lazy ? hat_dispatch<u32, true>(t, in, bhat, bhat_sets, out, batch, terms, out_prepared) : hat_dispatch<u32, false>(t, in, bhat, bhat_sets, out, batch, terms, out_prepared);
+  return emu_with_shape(t, [&](auto sh, auto bc) {
+    typedef decltype(sh) Sh;
+    constexpr bool BC = decltype(bc)::value;
+    return bhat ? polydot_hat_emu<Sh, BC>(t, in, bhat, bhat_sets, out, batch, terms, out_prepared) : unprepare_emu<Sh, BC>(t, in, out, batch);
+  });
 }
 
 }  // namespace

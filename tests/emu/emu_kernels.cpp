@@ -1,81 +1,15 @@
-// emu_kernels.cpp — TEST INFRASTRUCTURE: steps the product kernels' per-thread
-// code (tiny_ntt_amd/csrc/fused_core.h, modarith.h, plan_tables.h — the very
-// headers the gfx950 kernels are compiled from) on the CPU, one emulated thread
-// at a time with barriers between phases, so index maps, LDS layouts, table
-// semantics and lazy-reduction bounds can be checked in the GPU-less build
-// container.  Kernel variant, tables and constants of a fused launch and the
-// row planning come from launch_plan.h, the header the launchers take them from.  Built with g++ by tests/emu/Makefile; loaded by tests/test_emu.py.
-// It is not a product path and nothing in tiny_ntt_amd/ loads it.
-#include <stdint.h>
-#include <stddef.h>
-#include <vector>
-#include "../../tiny_ntt_amd/csrc/plan_tables.h"
+// emu_kernels.cpp — TEST INFRASTRUCTURE: steps the per-thread code of the product kernel, the standalone transforms and the
+// constant-geometry kernels (tiny_ntt_amd/csrc/fused_core.h, cg_core.h, modarith.h, plan_tables.h — the very headers the
+// gfx950 kernels are compiled from) on the CPU, one emulated thread at a time with barriers between phases, so index maps,
+// LDS layouts, table semantics and lazy-reduction bounds can be checked without a GPU; also the layout, schedule and
+// arithmetic probes.  The fused shape, tables and constants of a launch and the row planning come from launch_plan.h, the
+// header the launchers take them from (the Stepper and emu_with_shape: emu_stepper.h).  One of the five objects of
+// tests/emu/_build/libemu.so (tests/emu/Makefile); loaded by tests/conftest.py (Emu).  It is not a product path and nothing in
+// tiny_ntt_amd/ loads it.
+#include "emu_stepper.h"
 #include "../../tiny_ntt_amd/csrc/cg_core.h"
 
-using namespace tn;
-
 namespace {
-
-const std::vector<u64>& host_table(const HostTables& t, FusedTable w) {
-  switch (w) {
-    case FT_PSI_BRV: return t.psi_brv;
-    case FT_PSI_INV_BRV: return t.psi_inv_brv;
-    case FT_CYC_BRV: return t.cyc_brv;
-    case FT_CYC_INV_BRV: return t.cyc_inv_brv;
-    case FT_PSI_BC: return t.psi_bc;
-    case FT_CYC_BC: return t.cyc_bc;
-  }
-  return t.psi_brv;
-}
-
-// One workgroup of the fused kernels: every thread runs phase p, then all of them exchange through the LDS image.
-// BC: the base-case product's incomplete transform (fwd_phase / inv_phase).
-template <typename E, int LOGN, int LPT, typename Pol, bool BC = false> struct Stepper {
-  typedef FusedCfg<E, LOGN, LPT> Cfg;
-  typedef typename TwOf<E>::type Tw;
-  static constexpr u32 T = Cfg::THREADS;
-  struct Regs { E x[Cfg::R]; };
-  struct Pre { Tw t[Cfg::NPRE]; };
-  // a table in the plan's record format and the slice of it the kernel stages in LDS
-  struct Table {
-    std::vector<Tw> glob, lds;
-    Table(const HostTables& t, FusedTable w) : glob(h_fused_table<E>(host_table(t, w), t)), lds(glob.begin() + Cfg::lds_tw_lo(), glob.begin() + Cfg::lds_tw_hi()) {}
-  };
-  const Arith<E> ar;
-  std::vector<E> lds = std::vector<E>(Cfg::lds_elems());
-  std::vector<Pre> pre = std::vector<Pre>(T);        // the last phase's thread-private records of the transform stepped last
-
-  template <int EX, int FROM, int TO> void exchange(std::vector<Regs>& x) {
-    for (auto& v : lds) v = (E)0xDEADBEEFu;
-    for (u32 tau = 0; tau < T; ++tau) ex_store<E, Cfg, EX, FROM>(x[tau].x, tau, lds.data());
-    for (u32 tau = 0; tau < T; ++tau) ex_load<E, Cfg, EX, TO>(x[tau].x, tau, lds.data());
-  }
-  void forward(std::vector<Regs>& x, const Table& tab) {
-    for (u32 tau = 0; tau < T; ++tau) tw_prefetch<E, Cfg>(pre[tau].t, tau, tab.glob.data());
-    static_for<0, Cfg::PHASES>([&](auto p_) {
-      constexpr int p = decltype(p_)::value;
-      for (u32 tau = 0; tau < T; ++tau) {
-        const TwRefs<E> tw = {tab.glob.data(), tab.lds.data(), pre[tau].t};
-        fwd_phase<E, Cfg, Pol, p, BC>(x[tau].x, tau, tw, ar);
-      }
-      if constexpr (p + 1 < Cfg::PHASES) exchange<p, p, p + 1>(x);
-    });
-  }
-  void inverse(std::vector<Regs>& x, const Table& tab) {
-    for (u32 tau = 0; tau < T; ++tau) {
-      if constexpr (BC) for (auto& r : pre[tau].t) r = Tw{~(u64)0, ~(u64)0};      // records the base case's inverse must not read
-      tw_prefetch_stages<E, Cfg, Cfg::stage_begin(Cfg::PHASES - 1), BC ? LOGN - 1 : LOGN>(pre[tau].t, tau, tab.glob.data());
-    }
-    static_for<0, Cfg::PHASES>([&](auto i_) {
-      constexpr int p = Cfg::PHASES - 1 - decltype(i_)::value;
-      for (u32 tau = 0; tau < T; ++tau) {
-        const TwRefs<E> tw = {tab.glob.data(), tab.lds.data(), pre[tau].t};
-        inv_phase<E, Cfg, Pol, p, BC>(x[tau].x, tau, tw, ar);
-      }
-      if constexpr (p > 0) exchange<p - 1, p, p - 1>(x);
-    });
-  }
-};
 
 // Same steps as polymul_fused_kernel (kernels.hip), one emulated thread at a time; BC: its base-case instantiation.
 template <typename E, int LOGN, int LPT, bool LAZY, bool CIN = false, bool BC = false>
@@ -140,32 +74,6 @@ int fused_ntt_emu(const HostTables& t, int mode, const u64* in, u64* out) {
     nat[Cfg::nat_addr(bitrev(Cfg::jidx(LAST, tau, r), LOGN))] = LAZY ? Pol::canon(x[tau].x[r], ar) : x[tau].x[r];
   for (u32 tau = 0; tau < T; ++tau) for (int r = 0; r < Cfg::R; ++r) out[Cfg::jidx(0, tau, r)] = nat[Cfg::nat_addr(Cfg::jidx(0, tau, r))];
   return 0;
-}
-
-template <typename E, bool LAZY>
-int fused_ntt_dispatch(const HostTables& t, int mode, const u64* in, u64* out) {
-  switch (t.logn) {
-    case 8: return fused_ntt_emu<E, 8, fused_lpt(8), LAZY>(t, mode, in, out);
-    case 9: return fused_ntt_emu<E, 9, fused_lpt(9), LAZY>(t, mode, in, out);
-    case 10: return fused_ntt_emu<E, 10, fused_lpt(10), LAZY>(t, mode, in, out);
-    case 11: return fused_ntt_emu<E, 11, fused_lpt(11), LAZY>(t, mode, in, out);
-    case 12: return fused_ntt_emu<E, 12, fused_lpt(12), LAZY>(t, mode, in, out);
-    case 13: return fused_ntt_emu<E, 13, fused_lpt(13), LAZY>(t, mode, in, out);
-    default: return 7;
-  }
-}
-
-template <typename E, bool LAZY>
-int fused_dispatch(const HostTables& t, const u64* a, const u64* b, u64* c, size_t batch, bool cyclic) {
-  switch (t.logn) {
-    case 8: return fused_polymul_emu<E, 8, fused_lpt(8), LAZY>(t, a, b, c, batch, cyclic);
-    case 9: return fused_polymul_emu<E, 9, fused_lpt(9), LAZY>(t, a, b, c, batch, cyclic);
-    case 10: return fused_polymul_emu<E, 10, fused_lpt(10), LAZY>(t, a, b, c, batch, cyclic);
-    case 11: return fused_polymul_emu<E, 11, fused_lpt(11), LAZY>(t, a, b, c, batch, cyclic);
-    case 12: return fused_polymul_emu<E, 12, fused_lpt(12), LAZY>(t, a, b, c, batch, cyclic);
-    case 13: return fused_polymul_emu<E, 13, fused_lpt(13), LAZY>(t, a, b, c, batch, cyclic);
-    default: return 7;
-  }
 }
 
 // Sequential restatement of cg_kernel's arithmetic with the product's tables
@@ -352,11 +260,6 @@ template <typename E, int LOGN, int LPT> static long cfg_probe(int what, unsigne
   }
   return -1;
 }
-bool params_ok(u32 n, u64 q, u64 psi) {
-  if (n < 4 || (n & (n - 1)) || q < 3 || !(q & 1) || q >= ((u64)1 << 62)) return false;
-  return h_powmod(psi % q, n, q) == q - 1;
-}
-
 }  // namespace
 
 extern "C" {
@@ -372,16 +275,20 @@ int emu_fused_poly_mult(uint32_t n, uint64_t q, uint64_t psi, int flags, const u
     if (!(t.cin_ok && t.logn == 12 && t.lazy && t.elem_bytes == 8) || cyc) return 7;
     return fused_polymul_emu<u64, 12, fused_lpt(12), true, true>(t, a, b, c, batch, false);
   }
-  if (t.elem_bytes == 8) return t.lazy ? fused_dispatch<u64, true>(t, a, b, c, batch, cyc) : fused_dispatch<u64, false>(t, a, b, c, batch, cyc);
-  return t.lazy ? fused_dispatch<u32, true>(t, a, b, c, batch, cyc) : fused_dispatch<u32, false>(t, a, b, c, batch, cyc);
+  return emu_with_shape(t, [&](auto sh, auto) {           // (the base-case instantiation is stepped by bc_polymul)
+    typedef decltype(sh) Sh;
+    return fused_polymul_emu<typename Sh::E, Sh::LOGN, Sh::LPT, Sh::LAZY>(t, a, b, c, batch, cyc);
+  });
 }
 
 // mode: 0 twist + forward (natural out), 1 cg_ntt, 2 cg_intt — the register-tiled standalone transforms
 int emu_fused_ntt(uint32_t n, uint64_t q, uint64_t psi, int force_canonical, int mode, const uint64_t* in, uint64_t* out) {
   if (!params_ok(n, q, psi)) return 2;
   const HostTables t = h_build_tables(n, q, psi, !force_canonical);
-  if (t.elem_bytes == 8) return t.lazy ? fused_ntt_dispatch<u64, true>(t, mode, in, out) : fused_ntt_dispatch<u64, false>(t, mode, in, out);
-  return t.lazy ? fused_ntt_dispatch<u32, true>(t, mode, in, out) : fused_ntt_dispatch<u32, false>(t, mode, in, out);
+  return emu_with_shape(t, [&](auto sh, auto) {
+    typedef decltype(sh) Sh;
+    return fused_ntt_emu<typename Sh::E, Sh::LOGN, Sh::LPT, Sh::LAZY>(t, mode, in, out);
+  });
 }
 
 // ---- the product kernel's base-case instantiation (tests/test_basecase.py) ----
@@ -473,22 +380,10 @@ long emu_cgm_probe(int group, int layout, int what, unsigned x) {
 
 // see cfg_probe() above for `what`
 long emu_cfg_probe(int logn, int elem_bytes, int what, unsigned a0, unsigned a1, unsigned a2) {
-  if (elem_bytes == 8) {
-    if (logn == 8) return cfg_probe<u64, 8, fused_lpt(8)>(what, a0, a1, a2);
-    if (logn == 9) return cfg_probe<u64, 9, fused_lpt(9)>(what, a0, a1, a2);
-    if (logn == 10) return cfg_probe<u64, 10, fused_lpt(10)>(what, a0, a1, a2);
-    if (logn == 11) return cfg_probe<u64, 11, fused_lpt(11)>(what, a0, a1, a2);
-    if (logn == 12) return cfg_probe<u64, 12, fused_lpt(12)>(what, a0, a1, a2);
-    if (logn == 13) return cfg_probe<u64, 13, fused_lpt(13)>(what, a0, a1, a2);
-  } else {
-    if (logn == 8) return cfg_probe<u32, 8, fused_lpt(8)>(what, a0, a1, a2);
-    if (logn == 9) return cfg_probe<u32, 9, fused_lpt(9)>(what, a0, a1, a2);
-    if (logn == 10) return cfg_probe<u32, 10, fused_lpt(10)>(what, a0, a1, a2);
-    if (logn == 11) return cfg_probe<u32, 11, fused_lpt(11)>(what, a0, a1, a2);
-    if (logn == 12) return cfg_probe<u32, 12, fused_lpt(12)>(what, a0, a1, a2);
-    if (logn == 13) return cfg_probe<u32, 13, fused_lpt(13)>(what, a0, a1, a2);
-  }
-  return -1;
+  return with_fused_shape(elem_bytes, false, (u32)logn, -1L, [&](auto sh) {
+    typedef decltype(sh) Sh;
+    return cfg_probe<typename Sh::E, Sh::LOGN, Sh::LPT>(what, a0, a1, a2);
+  });
 }
 
 // Direct probes of the arithmetic primitives (for property tests).
@@ -526,15 +421,7 @@ long emu_split_sched_stat(int logn, int what) {
     for (int s = 0; s < C::LOGN; ++s) for (int r = 0; r < C::R; ++r) { f += S::D.ffold[s][r]; i += S::D.ifold[s][r]; }
     return what == 0 ? f : what == 1 ? i : what == 2 ? S::D.fout : (long)S::D.pw_fold_b;
   };
-  switch (logn) {
-    case 8: return stat(FusedCfg<u64, 8, fused_lpt(8)>());
-    case 9: return stat(FusedCfg<u64, 9, fused_lpt(9)>());
-    case 10: return stat(FusedCfg<u64, 10, fused_lpt(10)>());
-    case 11: return stat(FusedCfg<u64, 11, fused_lpt(11)>());
-    case 12: return stat(FusedCfg<u64, 12, fused_lpt(12)>());
-    case 13: return stat(FusedCfg<u64, 13, fused_lpt(13)>());
-  }
-  return -1;
+  return with_fused_shape(8, true, (u32)logn, -1L, [&](auto sh) { return stat(typename decltype(sh)::Cfg()); });
 }
 uint32_t emu_fold32(uint32_t x, uint32_t q) { const int k = h_bitlen(q); return fold(x, k, (u32)((((u64)1) << k) - q)); }
 

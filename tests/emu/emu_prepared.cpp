@@ -1,17 +1,19 @@
 // emu_prepared.cpp — TEST INFRASTRUCTURE: steps the prepared-operand kernels (prepare_fused_kernel, polymul_prepared_kernel:
-// tiny_ntt_amd/csrc/kernels_prepared.hip) on the CPU, one emulated thread at a time, with the Stepper of emu_kernels.cpp, the headers
-// the gfx950 kernels are compiled from and the prepared-order index map the kernels use (FusedCfg::prep_idx).  Kernel
-// variant, tables and constants come from fused_product_setup (launch_plan.h), as in the launchers.  Built into its own
-// library by tests/emu/Makefile.prepared; loaded by tests/test_prepared_emu.py and tests/test_gpu_prepared.py.
-#include "emu_kernels.cpp"
+// tiny_ntt_amd/csrc/kernels_prepared.hip) on the CPU, one emulated thread at a time, with the Stepper of emu_stepper.h, the headers
+// the gfx950 kernels are compiled from and the prepared-order index map the kernels use (FusedCfg::prep_idx).  Shape and base
+// case come from emu_with_shape, tables and constants from fused_product_setup (launch_plan.h), as in the launchers.  Part of
+// tests/emu/_build/libemu.so; used by tests/test_prepared_emu.py and tests/test_gpu_prepared.py.
+#include "emu_stepper.h"
 
 namespace {
 
 // Same steps as prepare_fused_kernel, one emulated thread at a time; BC: the plan's product runs the base case.
-template <typename E, int LOGN, int LPT, bool LAZY, bool BC>
+template <typename Sh, bool BC>
 int prepare_emu(const HostTables& t, const u64* b, u64* bhat, size_t rows) {
-  typedef Policy<E, LAZY> Pol;
-  typedef Stepper<E, LOGN, LPT, Pol, BC> S;
+  typedef typename Sh::E E;
+  constexpr int LOGN = Sh::LOGN;
+  typedef Policy<E, Sh::LAZY> Pol;
+  typedef Stepper<E, LOGN, Sh::LPT, Pol, BC> S;
   typedef typename S::Cfg Cfg;
   const FusedProductSetup<E> su = fused_product_setup(h_make_arith<E>(t), BC, false);
   S wg{su.ar};
@@ -31,10 +33,12 @@ int prepare_emu(const HostTables& t, const u64* b, u64* bhat, size_t rows) {
 }
 
 // Same steps as polymul_prepared_kernel (bhat_rows == 1: its SHARED instantiation, whose registers are loaded once).
-template <typename E, int LOGN, int LPT, bool LAZY, bool BC>
+template <typename Sh, bool BC>
 int polymul_prepared_emu(const HostTables& t, const u64* a, const u64* bhat, size_t bhat_rows, u64* c, size_t batch) {
-  typedef Policy<E, LAZY> Pol;
-  typedef Stepper<E, LOGN, LPT, Pol, BC> S;
+  typedef typename Sh::E E;
+  constexpr int LOGN = Sh::LOGN;
+  typedef Policy<E, Sh::LAZY> Pol;
+  typedef Stepper<E, LOGN, Sh::LPT, Pol, BC> S;
   typedef typename S::Cfg Cfg;
   const FusedProductSetup<E> su = fused_product_setup(h_make_arith<E>(t), BC, false);
   S wg{su.ar};
@@ -64,34 +68,15 @@ int polymul_prepared_emu(const HostTables& t, const u64* a, const u64* bhat, siz
   return 0;
 }
 
-// a == nullptr: prepare (in = b, out = bhat); otherwise the product.  The base case exactly where the launchers select it.
-template <typename E, int LOGN, bool LAZY>
-int prepared_shape(const HostTables& t, const u64* a, const u64* in, size_t in_rows, u64* out, size_t batch) {
-  constexpr int LPT = fused_lpt(LOGN);
-  if constexpr (fused_has_bc<E, LOGN, LPT, LAZY>()) {
-    if (t.bc_ok) return a ? polymul_prepared_emu<E, LOGN, LPT, LAZY, true>(t, a, in, in_rows, out, batch) : prepare_emu<E, LOGN, LPT, LAZY, true>(t, in, out, batch);
-  }
-  return a ? polymul_prepared_emu<E, LOGN, LPT, LAZY, false>(t, a, in, in_rows, out, batch) : prepare_emu<E, LOGN, LPT, LAZY, false>(t, in, out, batch);
-}
-
-template <typename E, bool LAZY>
-int prepared_dispatch(const HostTables& t, const u64* a, const u64* in, size_t in_rows, u64* out, size_t batch) {
-  switch (t.logn) {
-    case 8: return prepared_shape<E, 8, LAZY>(t, a, in, in_rows, out, batch);
-    case 9: return prepared_shape<E, 9, LAZY>(t, a, in, in_rows, out, batch);
-    case 10: return prepared_shape<E, 10, LAZY>(t, a, in, in_rows, out, batch);
-    case 11: return prepared_shape<E, 11, LAZY>(t, a, in, in_rows, out, batch);
-    case 12: return prepared_shape<E, 12, LAZY>(t, a, in, in_rows, out, batch);
-    case 13: return prepared_shape<E, 13, LAZY>(t, a, in, in_rows, out, batch);
-    default: return 7;
-  }
-}
-
+// a == nullptr: prepare (in = b, out = bhat); otherwise the product.
 int prepared_any(uint32_t n, uint64_t q, uint64_t psi, int flags, const u64* a, const u64* in, size_t in_rows, u64* out, size_t batch) {
   if (!params_ok(n, q, psi)) return 2;
   const HostTables t = h_build_tables(n, q, psi, !(flags & 1));
-  if (t.elem_bytes == 8) return t.lazy ? prepared_dispatch<u64, true>(t, a, in, in_rows, out, batch) : prepared_dispatch<u64, false>(t, a, in, in_rows, out, batch);
-  return t.lazy ? prepared_dispatch<u32, true>(t, a, in, in_rows, out, batch) : prepared_dispatch<u32, false>(t, a, in, in_rows, out, batch);
+  return emu_with_shape(t, [&](auto sh, auto bc) {
+    typedef decltype(sh) Sh;
+    constexpr bool BC = decltype(bc)::value;
+    return a ? polymul_prepared_emu<Sh, BC>(t, a, in, in_rows, out, batch) : prepare_emu<Sh, BC>(t, in, out, batch);
+  });
 }
 
 }  // namespace

@@ -1,6 +1,7 @@
-// Test infrastructure: the CPU stepping of the kernels' per-thread code (emu_kernels.cpp: the product's own headers compiled for the
-// host) run under AddressSanitizer + UndefinedBehaviorSanitizer.  GPU sanitizers are not available on the GPU pool, so this is where an
-// out-of-bounds LDS image / table index or a shift by the word size in fused_core.h / cg_core.h / plan_tables.h would show.
+// Test infrastructure: the CPU stepping of the kernels' per-thread code (emu_kernels.cpp, emu_prepared.cpp, emu_dot.cpp, emu_hat.cpp,
+// emu_gadget.cpp: the product's own headers compiled for the host) run under AddressSanitizer + UndefinedBehaviorSanitizer.  GPU sanitizers are not available on the GPU pool, so this is where an
+// out-of-bounds LDS image / table index or a shift by the word size in fused_core.h / cg_core.h / plan_tables.h would show:
+// the prepared-order index map (prep_idx), the zeta-record LDS layout of basecase_each and the carry mask of gadget_digit included.
 // Built and run by tests/test_emu.py::test_kernel_bodies_under_address_and_ub_sanitizers (tests/emu/Makefile: sanitize).
 #include <cstdint>
 #include <cstdio>
@@ -14,6 +15,18 @@ int emu_cg(uint32_t n, uint64_t q, uint64_t psi, int mode, const uint64_t* a, co
 int emu_cgm(uint32_t n, uint64_t q, uint64_t psi, int mode, int group, int layout, int am, int flags, const uint64_t* a, const uint64_t* b,
             uint64_t* out, uint64_t* trace);
 int bc_polymul(uint32_t n, uint64_t q, uint64_t psi, const uint64_t* a, const uint64_t* b, uint64_t* c, size_t batch, int cyclic);
+int emu_prepare(uint32_t n, uint64_t q, uint64_t psi, int flags, const uint64_t* b, uint64_t* bhat, size_t rows);
+int emu_poly_mult_prepared(uint32_t n, uint64_t q, uint64_t psi, int flags, const uint64_t* a, const uint64_t* bhat, size_t bhat_rows, uint64_t* c,
+                           size_t batch);
+int emu_poly_dot_prepared(uint32_t n, uint64_t q, uint64_t psi, int canonical, const uint64_t* a, const uint64_t* bhat, size_t bhat_sets, uint64_t* c,
+                          size_t batch, size_t terms);
+int emu_unprepare(uint32_t n, uint64_t q, uint64_t psi, int canonical, const uint64_t* xhat, uint64_t* x, size_t rows);
+int emu_poly_dot_hat(uint32_t n, uint64_t q, uint64_t psi, int canonical, const uint64_t* ahat, const uint64_t* bhat, size_t bhat_sets, uint64_t* out,
+                     size_t batch, size_t terms, int out_prepared);
+int emu_poly_gadget_dot_prepared(uint32_t n, uint64_t q, uint64_t psi, int canonical, const uint64_t* a, const uint64_t* bhat, size_t bhat_sets,
+                                 uint64_t* c, size_t batch, size_t terms, uint32_t base_log, uint32_t flags);
+int emu_gadget_digits(uint32_t n, uint64_t q, uint64_t psi, int canonical, const uint64_t* x, uint64_t* digits, size_t count, size_t terms,
+                      uint32_t base_log, uint32_t flags, int* lane_bytes, int* lazy);
 }
 
 namespace {
@@ -26,10 +39,95 @@ void expect(bool ok, const char* what, unsigned n, int a, int b, int c, int d) {
   ++checks;
   if (!ok) { ++failures; std::fprintf(stderr, "MISMATCH %s n=%u (%d %d %d %d)\n", what, n, a, b, c, d); }
 }
+struct P { uint32_t n; uint64_t q, psi; };
+typedef std::vector<uint64_t> Rows;
+
+// The prepared-operand, dot-product, transform-domain and gadget steppings of one plan under both policies: batch 2, terms 2,
+// one shared prepared set and one set per row, each result cross-checked against the stepping it is defined by.
+void family_cases(const P& p) {
+  const uint32_t n = p.n;
+  const uint64_t q = p.q;
+  const size_t batch = 2, terms = 2, rows = batch * terms;
+  const bool narrow = q < (1ull << 32);
+  Rows a(rows * n), b(rows * n);
+  for (size_t i = 0; i < rows * n; ++i) { a[i] = next() >> (narrow ? 32 : 0); b[i] = next() >> (narrow ? 32 : 0); }      // any word of the lane
+  a[0] = q - 1; b[0] = q - 1; a[1] = 0; b[n - 1] = ~0ull >> (narrow ? 32 : 0);
+  auto row = [n](const Rows& v, size_t r) { return v.data() + r * n; };
+  // references from the constant-geometry stepping: products of single rows and their sums mod q.  set 0: b shared, 1: per row
+  auto product = [&](size_t ar, size_t br) {
+    Rows c(n);
+    const int rc = emu_cg(n, q, p.psi, 2, row(a, ar), row(b, br), c.data(), nullptr);
+    expect(rc == 0, "emu_cg rc", n, rc, (int)ar, (int)br, 0);
+    return c;
+  };
+  Rows prod[2] = {Rows(rows * n), Rows(rows * n)}, dot[2] = {Rows(batch * n), Rows(batch * n)};
+  for (int per_row = 0; per_row < 2; ++per_row)
+    for (size_t r = 0; r < batch; ++r) for (size_t j = 0; j < terms; ++j) {
+      const Rows c = product(r * terms + j, per_row ? r * terms + j : j);
+      for (uint32_t i = 0; i < n; ++i) {
+        prod[per_row][(r * terms + j) * n + i] = c[i];
+        uint64_t& s = dot[per_row][r * n + i];
+        s = (uint64_t)(((unsigned __int128)s + c[i]) % q);
+      }
+    }
+  const uint32_t base_log = narrow ? 12 : 30;              // two digits cover q: 2^base_log < q and 2 base_log >= bits of q
+  for (int canon : {0, 1}) {
+    Rows ahat(rows * n), bhat(rows * n), out(rows * n), x(rows * n);
+    int r = emu_prepare(n, q, p.psi, canon, a.data(), ahat.data(), rows);
+    r |= emu_prepare(n, q, p.psi, canon, b.data(), bhat.data(), rows);
+    expect(r == 0, "prepare", n, canon, r, 0, 0);
+    // hat: unprepare(prepare(x)) = x mod q
+    r = emu_unprepare(n, q, p.psi, canon, ahat.data(), x.data(), rows);
+    bool ok = r == 0;
+    for (size_t i = 0; i < rows * n && ok; ++i) ok = x[i] == a[i] % q;
+    expect(ok, "unprepare(prepare)", n, canon, r, 0, 0);
+    for (int per_row = 0; per_row < 2; ++per_row) {
+      const size_t sets = per_row ? batch : 1;
+      // prepared: every product against b's prepared row(s).  Shared: ONE prepared row, so row j of the shared set is stepped
+      // as its own call over the a-rows that meet it.
+      if (per_row) {
+        std::fill(out.begin(), out.end(), 0);
+        r = emu_poly_mult_prepared(n, q, p.psi, canon, a.data(), bhat.data(), rows, out.data(), rows);
+        expect(r == 0 && out == prod[1], "prepared product, a row each", n, canon, r, 0, 0);
+      } else {
+        for (size_t j = 0; j < terms; ++j) {
+          Rows aj(batch * n), cj(batch * n), want(batch * n);
+          for (size_t rr = 0; rr < batch; ++rr) {
+            std::memcpy(aj.data() + rr * n, row(a, rr * terms + j), n * sizeof(uint64_t));
+            std::memcpy(want.data() + rr * n, row(prod[0], rr * terms + j), n * sizeof(uint64_t));
+          }
+          r = emu_poly_mult_prepared(n, q, p.psi, canon, aj.data(), row(bhat, j), 1, cj.data(), batch);
+          expect(r == 0 && cj == want, "prepared product, shared row", n, canon, r, (int)j, 0);
+        }
+      }
+      // dot: the sum mod q of those products
+      Rows c(batch * n), chat(batch * n), want_hat(batch * n);
+      r = emu_poly_dot_prepared(n, q, p.psi, canon, a.data(), bhat.data(), sets, c.data(), batch, terms);
+      expect(r == 0 && c == dot[per_row], "prepared dot product", n, canon, per_row, r, 0);
+      // hat: the same from prepared operands, and left prepared
+      std::fill(c.begin(), c.end(), 0);
+      r = emu_poly_dot_hat(n, q, p.psi, canon, ahat.data(), bhat.data(), sets, c.data(), batch, terms, 0);
+      expect(r == 0 && c == dot[per_row], "transform-domain dot product", n, canon, per_row, r, 0);
+      r = emu_poly_dot_hat(n, q, p.psi, canon, ahat.data(), bhat.data(), sets, chat.data(), batch, terms, 1);
+      r |= emu_prepare(n, q, p.psi, canon, dot[per_row].data(), want_hat.data(), batch);
+      expect(r == 0 && chat == want_hat, "transform-domain dot product, prepared out", n, canon, per_row, r, 0);
+      // gadget: the kernel that cuts the digits itself against the dot product on the rows of emu_gadget_digits
+      for (uint32_t balanced : {0u, 1u}) {
+        Rows words(batch * n), digits(batch * n * terms), drows(rows * n), want(batch * n), got(batch * n);
+        for (size_t rr = 0; rr < batch; ++rr) std::memcpy(words.data() + rr * n, row(a, rr * terms), n * sizeof(uint64_t));
+        r = emu_gadget_digits(n, q, p.psi, canon, words.data(), digits.data(), batch * n, terms, base_log, balanced, nullptr, nullptr);
+        for (size_t rr = 0; rr < batch; ++rr) for (size_t j = 0; j < terms; ++j) for (uint32_t i = 0; i < n; ++i)
+          drows[(rr * terms + j) * n + i] = digits[(rr * n + i) * terms + j];
+        r |= emu_poly_dot_prepared(n, q, p.psi, canon, drows.data(), bhat.data(), sets, want.data(), batch, terms);
+        const int r2 = emu_poly_gadget_dot_prepared(n, q, p.psi, canon, words.data(), bhat.data(), sets, got.data(), batch, terms, base_log, balanced);
+        expect(r == 0 && r2 == 0 && got == want, "gadget dot product", n, canon, per_row, (int)balanced, r | r2);
+      }
+    }
+  }
+}
 }  // namespace
 
 int main() {
-  struct P { uint32_t n; uint64_t q, psi; };
   // psi of the full-size sets squared down to smaller n (psi^(N/n) is a primitive 2n-th root)
   const P base24 = {4096, 8380417ull, 283817ull}, base60 = {4096, 1152921504606830593ull, 431606828070683274ull};
   std::vector<P> sets;
@@ -87,6 +185,9 @@ int main() {
       }
     }
   }
+  // the four later families at their smallest shapes: 32-bit lanes, 64-bit lanes, and the one base-case shape
+  for (const P& p : sets)
+    if ((p.n == 256) || (p.n == base60.n && p.q == base60.q)) family_cases(p);
   std::printf("sanitize_driver: %zu parameter sets, %d checks, %d failures\n", sets.size(), checks, failures);
   return failures ? 1 : 0;
 }

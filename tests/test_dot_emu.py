@@ -1,26 +1,22 @@
 """CPU stepping of the prepared dot-product kernel (tests/emu/emu_dot.cpp: polydot_prepared_kernel stepped thread by thread
 with the kernel's own headers, accumulate function and prepared-order index map) against the oracle, without a GPU."""
 import ctypes
-import os
 
 import numpy as np
 import pytest
 
-from conftest import PARAMS, ROOT, P64, _make, ntt_prime_below, p64
+import emu_library
+from conftest import PARAMS, P64, ntt_prime_below, p64
 from test_prepared_emu import CASES, CASE_IDS, EmuPrepared, _case_data, operand_rows
 
 POLICIES = pytest.mark.parametrize("canonical", [False, True], ids=["lazy", "canonical"])
 
 
 class EmuDot:
-    """ctypes view of tests/emu/_build/libemu_dot.so."""
+    """The prepared dot-product entry points of tests/emu/_build/libemu.so (tests/emu/emu_dot.cpp)."""
 
     def __init__(self):
-        so = os.path.join(ROOT, "tests", "emu", "_build", "libemu_dot.so")
-        assert os.path.exists(os.path.join(ROOT, "tests", "emu", "Makefile.dot"))
-        if not os.path.exists(so):
-            _make("tests/emu", "-f", "Makefile.dot")
-        L = self.lib = ctypes.CDLL(so)
+        L = self.lib = emu_library.load()
         u32, u64, sz, ci = ctypes.c_uint32, ctypes.c_uint64, ctypes.c_size_t, ctypes.c_int
         L.emu_poly_dot_prepared.argtypes = [u32, u64, u64, ci, P64, P64, sz, P64, sz, sz]
         L.emu_dot_accumulate.argtypes = [u32, u64, u64, ci, P64, P64, P64, sz, ctypes.POINTER(ci), ctypes.POINTER(ci)]

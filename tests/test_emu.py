@@ -346,17 +346,20 @@ def test_kernel_bodies_under_address_and_ub_sanitizers():
     """GPU sanitizers are not available on the pool: the kernels' per-thread code (the product's own headers, stepped on the CPU by
     tests/emu) runs under AddressSanitizer + UndefinedBehaviorSanitizer instead - every LDS image / table index, every shift count
     of fused_core.h, cg_core.h and plan_tables.h for n = 16 ... 4096, both lane widths, every GROUP x layout x arithmetic of the
-    constant-geometry trips, fused products and transforms.  The driver also cross-checks every result (tests/emu/sanitize_driver.cpp)."""
+    constant-geometry trips, fused products and transforms; and the prepared-operand, dot-product, transform-domain and gadget
+    steppings (prep_idx, the zeta-record LDS layout of basecase_each, the carry mask of gadget_digit) at n = 256 with 32-bit and
+    64-bit lanes and at the base-case shape, both policies, batch 2 x 2 terms, one shared prepared set and one per row.  The driver
+    also cross-checks every result (tests/emu/sanitize_driver.cpp).  It is a stand-alone program: nothing is loaded into Python."""
     import subprocess
     d = os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu")
-    b = subprocess.run(["make", "-C", d, "sanitize"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    b = subprocess.run(["make", "-j8", "-C", d, "sanitize"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     assert b.returncode == 0, b.stdout[-2000:]
     r = subprocess.run([os.path.join(d, "_build", "sanitize_driver")], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
                        env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1"))
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
     assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-3000:]
     m = __import__("re").search(r"(\d+) checks, 0 failures", r.stdout)
-    assert m and int(m.group(1)) > 1500, r.stdout
+    assert m and int(m.group(1)) > 2650, r.stdout
 
 
 @pytest.mark.parametrize("n,q", __import__("chosen_rows").SHAPES)

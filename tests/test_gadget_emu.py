@@ -2,12 +2,12 @@
 the kernel's own headers and its canonicalise-and-digit functions) against the definition of include/tinyntt.h written out in
 Python with big integers, the stepping of the prepared dot product on those digits, and the oracle, without a GPU."""
 import ctypes
-import os
 
 import numpy as np
 import pytest
 
-from conftest import PARAMS, ROOT, P64, _make, p64
+import emu_library
+from conftest import PARAMS, P64, p64
 from test_dot_emu import EmuDot, sum_mod, term_rows
 from test_prepared_emu import CASES, CASE_IDS, EmuPrepared, _case_data
 
@@ -16,14 +16,10 @@ MODES = (False, True)                      # unsigned, balanced
 
 
 class EmuGadget:
-    """ctypes view of tests/emu/_build/libemu_gadget.so."""
+    """The gadget entry points of tests/emu/_build/libemu.so (tests/emu/emu_gadget.cpp)."""
 
     def __init__(self):
-        so = os.path.join(ROOT, "tests", "emu", "_build", "libemu_gadget.so")
-        assert os.path.exists(os.path.join(ROOT, "tests", "emu", "Makefile.gadget"))
-        if not os.path.exists(so):
-            _make("tests/emu", "-f", "Makefile.gadget")
-        L = self.lib = ctypes.CDLL(so)
+        L = self.lib = emu_library.load()
         u32, u64, sz, ci = ctypes.c_uint32, ctypes.c_uint64, ctypes.c_size_t, ctypes.c_int
         L.emu_poly_gadget_dot_prepared.argtypes = [u32, u64, u64, ci, P64, P64, sz, P64, sz, sz, u32, u32]
         L.emu_gadget_digits.argtypes = [u32, u64, u64, ci, P64, P64, sz, sz, u32, u32, ctypes.POINTER(ci), ctypes.POINTER(ci)]

@@ -2,12 +2,12 @@
 thread by thread with the kernels' own headers, product and accumulate functions and prepared-order index map) against the
 oracle and against the stepping of the prepare and prepared dot-product kernels, without a GPU."""
 import ctypes
-import os
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, P64, _make, p64
+import emu_library
+from conftest import P64, p64
 from test_dot_emu import EmuDot, dot_reference, products, term_rows          # noqa: F401  (products: a fixture)
 from test_prepared_emu import CASES, CASE_IDS, EmuPrepared, _case_data
 
@@ -15,14 +15,10 @@ POLICIES = pytest.mark.parametrize("canonical", [False, True], ids=["lazy", "can
 
 
 class EmuHat:
-    """ctypes view of tests/emu/_build/libemu_hat.so."""
+    """The transform-domain entry points of tests/emu/_build/libemu.so (tests/emu/emu_hat.cpp)."""
 
     def __init__(self):
-        so = os.path.join(ROOT, "tests", "emu", "_build", "libemu_hat.so")
-        assert os.path.exists(os.path.join(ROOT, "tests", "emu", "Makefile.hat"))
-        if not os.path.exists(so):
-            _make("tests/emu", "-f", "Makefile.hat")
-        L = self.lib = ctypes.CDLL(so)
+        L = self.lib = emu_library.load()
         u32, u64, sz, ci = ctypes.c_uint32, ctypes.c_uint64, ctypes.c_size_t, ctypes.c_int
         L.emu_unprepare.argtypes = [u32, u64, u64, ci, P64, P64, sz]
         L.emu_poly_dot_hat.argtypes = [u32, u64, u64, ci, P64, P64, sz, P64, sz, sz, ci]

@@ -9,19 +9,17 @@ import os
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, PARAMS, ROOT, P64, _make, ntt_prime_below, p64
+import emu_library
+from conftest import GOLDEN, PARAMS, P64, ntt_prime_below, p64
 
 Q23, Q60 = 8380417, 1152921504606830593          # the reference's two moduli
 
 
 class EmuPrepared:
-    """ctypes view of tests/emu/_build/libemu_prepared.so."""
+    """The prepared-operand entry points of tests/emu/_build/libemu.so (tests/emu/emu_prepared.cpp)."""
 
     def __init__(self):
-        so = os.path.join(ROOT, "tests", "emu", "_build", "libemu_prepared.so")
-        if not os.path.exists(so):
-            _make("tests/emu", "-f", "Makefile.prepared")
-        L = self.lib = ctypes.CDLL(so)
+        L = self.lib = emu_library.load()
         u32, u64, sz, ci = ctypes.c_uint32, ctypes.c_uint64, ctypes.c_size_t, ctypes.c_int
         L.emu_prepare.argtypes = [u32, u64, u64, ci, P64, P64, sz]
         L.emu_poly_mult_prepared.argtypes = [u32, u64, u64, ci, P64, P64, sz, P64, sz]

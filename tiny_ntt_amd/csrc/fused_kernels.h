@@ -353,54 +353,31 @@ __device__ __forceinline__ void dot_last_term(E (&acc)[Cfg::R], E (&xa)[Cfg::R],
 // ============================================================================
 // Host side of every fused launcher
 // ============================================================================
-// A fused shape as a type: what dispatch_fused_shape hands to a launcher.
-template <typename E_, int LOGN_, bool LAZY_> struct FusedShape {
-  typedef E_ E;
-  static constexpr int LOGN = LOGN_, LPT = fused_lpt(LOGN_);
-  static constexpr bool LAZY = LAZY_;
-  typedef FusedCfg<E_, LOGN_, LPT> Cfg;
-};
-
-// f(FusedShape of the plan), or hipErrorInvalidValue for a plan without fused kernels.  The one place that names the shapes.
-// PRODUCT: the caller is the product launcher.  Developer builds with -DTN_ONLY_MAIN (tools/asm_main.sh) instantiate only
-// its n = 4096 / 64-bit lazy shape; every other launcher returns hipErrorInvalidValue there and instantiates nothing.
+// f(FusedShape of the plan), or hipErrorInvalidValue for a plan without fused kernels.  The shapes are named in launch_plan.h
+// (with_fused_shape).  PRODUCT: the caller is the product launcher.  Developer builds with -DTN_ONLY_MAIN (tools/asm_main.sh)
+// instantiate only its n = 4096 / 64-bit lazy shape; every other launcher returns hipErrorInvalidValue there and instantiates
+// nothing.
 template <bool PRODUCT = false, typename F>
 inline hipError_t dispatch_fused_shape(const tn_plan* p, F&& f) {
 #ifdef TN_ONLY_MAIN
   if constexpr (PRODUCT) { if (p->elem_bytes == 8 && p->lazy && p->logn == 12) return f(FusedShape<u64, 12, true>()); }
   return hipErrorInvalidValue;
 #else
-  auto by_logn = [&](auto e_, auto lazy_) -> hipError_t {
-    typedef decltype(e_) E;
-    constexpr bool LAZY = decltype(lazy_)::value;
-    switch (p->logn) {
-      case 8: return f(FusedShape<E, 8, LAZY>());
-      case 9: return f(FusedShape<E, 9, LAZY>());
-      case 10: return f(FusedShape<E, 10, LAZY>());
-      case 11: return f(FusedShape<E, 11, LAZY>());
-      case 12: return f(FusedShape<E, 12, LAZY>());
-      case 13: return f(FusedShape<E, 13, LAZY>());
-      default: return hipErrorInvalidValue;
-    }
-  };
-  if (p->elem_bytes == 8) return p->lazy ? by_logn(u64(), std::true_type()) : by_logn(u64(), std::false_type());
-  return p->lazy ? by_logn(u32(), std::true_type()) : by_logn(u32(), std::false_type());
+  return with_fused_shape(p->elem_bytes, p->lazy, p->logn, hipErrorInvalidValue, f);
 #endif
 }
 
-// What a launch of the product family (product, prepared operand, transform domain, gadget) takes from the plan.  The base
-// case runs for plans whose (k, c) passes h_bc_sched_ok() (bc_ok) at the one shape that has it, in EVERY kernel of the
-// family: a prepared row is the product kernel's xb, so the formats agree only if they all choose alike.  no_bc: the product
-// launcher's promised-canonical-inputs kernel takes precedence (launch_fused_t).
+// What a launch of the product family (product, prepared operand, transform domain, gadget) takes from the plan; use_bc by
+// the family's one rule (launch_plan.h: fused_use_bc).
 template <typename Sh> struct FusedProductLaunch {
   typedef typename Sh::E E;
   typedef typename TwOf<E>::type Tw;
-  static constexpr bool HAS_BC = fused_has_bc<E, Sh::LOGN, Sh::LPT, Sh::LAZY>();
+  static constexpr bool HAS_BC = Sh::HAS_BC;
   const PlanView<E> pv;
   const bool use_bc;
   const FusedProductSetup<E> su;
   explicit FusedProductLaunch(const tn_plan* p, bool cyclic = false, bool no_bc = false)
-      : pv(make_view<E>(p)), use_bc(HAS_BC && p->bc_ok && !no_bc), su(fused_product_setup(pv.ar, use_bc, cyclic)) {}
+      : pv(make_view<E>(p)), use_bc(fused_use_bc<Sh>(p->bc_ok, no_bc)), su(fused_product_setup(pv.ar, use_bc, cyclic)) {}
   const Tw* fwd() const { return fused_table(pv, su.fwd); }
   const Tw* inv() const { return fused_table(pv, su.inv); }
 };

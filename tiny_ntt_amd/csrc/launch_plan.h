@@ -1,6 +1,6 @@
 // launch_plan.h — what a launch of the persistent kernels decides on the host, as plain functions without the HIP runtime:
-// which fused kernel variant, tables and constants (fused_product_setup, fused_ntt_setup) and how rows are handed out
-// (plan_rows).  The launchers (kernels*.hip, cg_kernel_impl.h through plan.h: launch_persistent) and the CPU stepping of
+// which fused shape (with_fused_shape) and whether its base case runs (fused_use_bc), which tables and constants
+// (fused_product_setup, fused_ntt_setup) and how rows are handed out (plan_rows).  The launchers (kernels*.hip, cg_kernel_impl.h through plan.h: launch_persistent) and the CPU stepping of
 // tests/emu both take their decisions from here, so the CPU tests check what the launchers do.
 #pragma once
 #include <stddef.h>
@@ -38,9 +38,50 @@ template <typename E, int LOGN, int LPT, bool LAZY> constexpr bool fused_has_bc(
   return sizeof(E) == 8 && LOGN == FUSED_BC_LOGN && LPT == 3 && LAZY;
 }
 
-// Product launch.  bc: this launch runs the base-case kernel (a shape with fused_has_bc(), a plan with bc_ok, and no
-// promised-canonical-inputs kernel taking precedence: launch_fused_t).  Then the forward table is psi_bc / cyc_bc, whose last
-// level holds the base case's zeta records, and the inverse runs log2(n) - 1 stages: (n/2)^-1 in place of n^-1.
+// A fused shape as a type: what with_fused_shape hands to a launcher or to the CPU stepping.
+template <typename E_, int LOGN_, bool LAZY_> struct FusedShape {
+  typedef E_ E;
+  static constexpr int LOGN = LOGN_, LPT = fused_lpt(LOGN_);
+  static constexpr bool LAZY = LAZY_, HAS_BC = fused_has_bc<E_, LOGN_, LPT, LAZY_>();
+  typedef FusedCfg<E_, LOGN_, LPT> Cfg;
+};
+
+// f(lane type, std::true_type / std::false_type for the lazy policy) of a plan's (elem_bytes, lazy): for what depends on the
+// arithmetic only.
+template <typename F>
+inline auto with_lane_policy(int elem_bytes, bool lazy, F&& f) {
+  if (elem_bytes == 8) return lazy ? f(u64(), std::true_type()) : f(u64(), std::false_type());
+  return lazy ? f(u32(), std::true_type()) : f(u32(), std::false_type());
+}
+
+// f(FusedShape of (elem_bytes, lazy, logn)), or `none` where no fused kernel is built for that n.  The one place that names
+// the shapes: the launchers come here through dispatch_fused_shape (fused_kernels.h), the CPU stepping through emu_with_shape
+// (tests/emu/emu_stepper.h).
+template <typename R, typename F>
+inline R with_fused_shape(int elem_bytes, bool lazy, u32 logn, R none, F&& f) {
+  return with_lane_policy(elem_bytes, lazy, [&](auto e_, auto lazy_) -> R {
+    typedef decltype(e_) E;
+    constexpr bool LAZY = decltype(lazy_)::value;
+    switch (logn) {
+      case 8: return f(FusedShape<E, 8, LAZY>());
+      case 9: return f(FusedShape<E, 9, LAZY>());
+      case 10: return f(FusedShape<E, 10, LAZY>());
+      case 11: return f(FusedShape<E, 11, LAZY>());
+      case 12: return f(FusedShape<E, 12, LAZY>());
+      case 13: return f(FusedShape<E, 13, LAZY>());
+      default: return none;
+    }
+  });
+}
+
+// The base case runs for plans whose (k, c) passes h_bc_sched_ok() (bc_ok) at the one shape that has it, in EVERY kernel of the
+// product family (product, prepared operand, transform domain, gadget): a prepared row is the product kernel's xb, so the
+// formats agree only if they all choose alike.  no_bc: the product launcher's promised-canonical-inputs kernel takes
+// precedence (launch_fused_t).
+template <typename Sh> constexpr bool fused_use_bc(bool bc_ok, bool no_bc = false) { return Sh::HAS_BC && bc_ok && !no_bc; }
+
+// Product launch.  bc: this launch runs the base-case kernel (fused_use_bc).  Then the forward table is psi_bc / cyc_bc, whose
+// last level holds the base case's zeta records, and the inverse runs log2(n) - 1 stages: (n/2)^-1 in place of n^-1.
 // cyclic = product in Z_q[x]/(x^n - 1) (python_poly_mult, test_ntt_poly_mult.py:38-43): same kernel, twiddle tables of the
 // x^n - 1 factorisation tree (HostTables::cyc_brv), whose inverse table has entry 1 equal to 1.
 template <typename E> struct FusedProductSetup { bool bc; Arith<E> ar; FusedTable fwd, inv; };
