@@ -346,6 +346,14 @@ int emu_is_lazy(uint32_t n, uint64_t q, uint64_t psi) {
   return h_build_tables(n, q, psi, true).lazy ? 1 : 0;
 }
 
+// The policy flags h_build_tables decides for a plan (n, q, psi): bit 0 lazy, 1 cg_lazy, 2 cg_sched, 3 cin_ok, 4 bc_ok; -1 for
+// bad parameters.  (tests/policy_moduli.py's FLAG_ENTRIES and tools/find_policy_moduli.py read every flag from here.)
+int emu_plan_flags(uint32_t n, uint64_t q, uint64_t psi) {
+  if (!params_ok(n, q, psi)) return -1;
+  const HostTables t = h_build_tables(n, q, psi, true);
+  return (t.lazy ? 1 : 0) | (t.cg_lazy ? 2 : 0) | (t.cg_sched ? 4 : 0) | (t.cin_ok ? 8 : 0) | (t.bc_ok ? 16 : 0);
+}
+
 // mode: 0 cg_ntt, 1 cg_intt, 2 nwc_poly_mult, 3 twist + cg_ntt.  trace may be NULL ([logn][n] otherwise, mode 0/3).
 int emu_cg(uint32_t n, uint64_t q, uint64_t psi, int mode, const uint64_t* a, const uint64_t* b, uint64_t* out, uint64_t* trace) {
   if (!params_ok(n, q, psi)) return 2;

@@ -8,7 +8,21 @@ refuse), the word-size points of the modulus sweeps (the largest NTT prime below
 
 The numbers are literals: finding a boundary means visiting NTT primes, which is too slow for a test.  They were printed by
 tools/find_policy_moduli.py, and tests/test_policy_moduli_emu.py::test_table_flags_and_boundary_pairs checks every flag and
-every pair (one prime step each), so a change to a bound schedule that moves a boundary fails there and names the pair."""
+every pair (one prime step each), so a change to a bound schedule that moves a boundary fails there and names the pair.
+
+CG_PAIRS, CIN_PAIRS, MID_PAIRS and FLAG_ENTRIES cover the replays that PAIRS does not.  HostTables carries five flags: lazy, cg_lazy
+(h_cg_lazy_ok), cg_sched (h_cg_sched_ok: the constant-geometry kernels with the static fold schedule, run at n = 4096), cin
+(h_split_sched_cin_ok: the n = 4096 product kernel for promised-canonical inputs) and bc.  CG_PAIRS and CIN_PAIRS hold, for n = 4096,
+the boundary pairs of cg_sched and cin where they are not the lazy policy's own pair: cg_sched at k = 59 and 60, cin at k = 60.  No pair
+is committed for a flag that has no boundary of its own: cg_lazy equals lazy wherever the lanes are 64 bits wide, cg_sched and cin end
+with lazy at k = 50 and 55, and all three are off with 32-bit lanes (k = 23, 26, 28); the self-check asserts exactly that at the
+committed lazy pairs.  MID_PAIRS holds the lazy pairs of n = 512, 1024 and 2048 at k = 26 and 60.  FLAG_ENTRIES lists every prime of
+those pairs, the n = 4096 lazy and bc pair primes at k = 59 and 60 and Q60 with all five flags: at n = 4096 / k = 60 the nested regions
+all flags, no cin, no cin or cg_sched, lazy only, none; at k = 59 all flags, no cg_sched, no cg_sched or bc, none (cin ends with lazy
+there).  Printed by tools/find_policy_moduli.py --tables flags (bisection and --walk agree), re-derived from tests/emu's
+emu_plan_flags by tests/test_policy_flags_emu.py::test_flag_tables_and_boundary_pairs, stepped on the CPU by the rest of that file
+and run on the GPU by tests/test_gpu_policy_flags.py (all but the cin kernel itself: the library is built without it, TN_FUSED_CIN = 0,
+so only the CPU stepping and the replay guard that instantiation)."""
 from chosen_rows import Q23, Q60, psi_of          # noqa: F401  (psi_of: psi of a plan of this table, for its users)
 
 # (n, flag, last prime = 1 (mod 2n) with the flag walking down from 2^k, first without it)
@@ -131,6 +145,55 @@ ENTRIES = [
     (8192, 3274297073082089473, False, False),
     (8192, 4611686018427322369, False, False),
 ]
+
+# ---- the other replays of plan_tables.h: cg_sched (h_cg_sched_ok), cin (h_split_sched_cin_ok), and n = 512 / 1024 / 2048 ----
+# Same shape as PAIRS.  Only boundaries that are not the lazy policy's own are listed (docstring above).
+CG_PAIRS = [
+    (4096, "cg_sched", 576460752241991681, 576460752241360897),
+    (4096, "cg_sched", 1152921504583507969, 1152921504583262209),
+]
+CIN_PAIRS = [
+    (4096, "cin", 1152921504603676673, 1152921504603381761),
+]
+MID_PAIRS = [
+    (512, "lazy", 66097153, 66091009),
+    (512, "lazy", 1152921504571058177, 1152921504571045889),
+    (1024, "lazy", 66097153, 66091009),
+    (1024, "lazy", 1152921504571058177, 1152921504571045889),
+    (2048, "lazy", 66097153, 66052097),
+    (2048, "lazy", 1152921504571146241, 1152921504571035649),
+]
+# (n, q, lazy, cg_lazy, cg_sched, cin, bc)
+FLAG_ENTRIES = [
+    (512, 66091009, False, False, False, False, False),
+    (512, 66097153, True, False, False, False, False),
+    (512, 1152921504571045889, False, False, False, False, False),
+    (512, 1152921504571058177, True, True, False, False, False),
+    (1024, 66091009, False, False, False, False, False),
+    (1024, 66097153, True, False, False, False, False),
+    (1024, 1152921504571045889, False, False, False, False, False),
+    (1024, 1152921504571058177, True, True, False, False, False),
+    (2048, 66052097, False, False, False, False, False),
+    (2048, 66097153, True, False, False, False, False),
+    (2048, 1152921504571035649, False, False, False, False, False),
+    (2048, 1152921504571146241, True, True, False, False, False),
+    (4096, 576460752236290049, False, False, False, False, False),
+    (4096, 576460752236388353, True, True, False, True, False),
+    (4096, 576460752241033217, True, True, False, True, False),
+    (4096, 576460752241082369, True, True, False, True, True),
+    (4096, 576460752241360897, True, True, False, True, True),
+    (4096, 576460752241991681, True, True, True, True, True),
+    (4096, 1152921504570802177, False, False, False, False, False),
+    (4096, 1152921504571146241, True, True, False, False, False),
+    (4096, 1152921504576864257, True, True, False, False, False),
+    (4096, 1152921504577118209, True, True, False, False, True),
+    (4096, 1152921504583262209, True, True, False, False, True),
+    (4096, 1152921504583507969, True, True, True, False, True),
+    (4096, 1152921504603381761, True, True, True, False, True),
+    (4096, 1152921504603676673, True, True, True, True, True),
+    (4096, 1152921504606830593, True, True, True, True, True),
+]
+FLAG_NAMES = ("lazy", "cg_lazy", "cg_sched", "cin", "bc")      # columns 2.. of FLAG_ENTRIES = bits 0.. of tests/emu's emu_plan_flags
 
 WORD_K = (20, 31, 32, 33, 41, 47, 61, 62)          # word lengths of the word-size points (two entries per n and k)
 

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from conftest import PARAMS
+from emu_library import smallest_dynamic_batch
 from test_dot_emu import term_rows
 from test_gadget_emu import MODES, EmuGadget, decompose_rows, gadget_pairs
 from test_prepared_emu import CASES, CASE_IDS, _case_data
@@ -124,17 +125,8 @@ def test_dynamic_row_hand_out(eng, emu, gadget):
     n, q, psi = PARAMS["P4096_60"]
     plan = eng.get_plan(n, q, psi)
     terms, w = 2, 30
-    L = emu.lib
-    sz, ci = ctypes.c_size_t, ctypes.c_int
-    L.emu_plan_rows.argtypes = [ci, sz, sz, sz, ctypes.POINTER(ctypes.c_uint32)]
-    L.emu_row_policy.argtypes = [ci, ci]; L.emu_row_policy.restype = ctypes.c_long
     resident = 4 * torch.cuda.get_device_properties(0).multi_processor_count
-    chunk = ctypes.c_uint32()
-    row_bytes = terms * n * plan.elem_bytes
-    want = max(1, -(-L.emu_row_policy(0, 0) // row_bytes))
-    rows = L.emu_row_policy(0, 1) * resident * want
-    assert L.emu_plan_rows(0, row_bytes, rows, resident, ctypes.byref(chunk)) == 1 and chunk.value == want
-    assert L.emu_plan_rows(0, row_bytes, rows - 1, resident, ctypes.byref(chunk)) == 0
+    rows = smallest_dynamic_batch(terms * n * plan.elem_bytes, resident)
     a = plan.fill_lcg(rows, 1, 2); b = plan.fill_lcg(rows * terms, 2, 2)
     per_set, shared = plan.prepare(b), plan.prepare(b[:terms])
     digits = plan.gadget_decompose(a, terms, w, True)

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from conftest import PARAMS
+from emu_library import smallest_dynamic_batch
 from test_dot_emu import sum_mod, term_rows
 from test_gpu_dot import device_sum
 from test_hat_emu import EmuHat
@@ -152,19 +153,10 @@ def test_dynamic_row_hand_out(eng, emu, oracle):
     n, q, psi = PARAMS["P4096_60"]
     plan = eng.get_plan(n, q, psi)
     terms = 2
-    L = emu.lib
-    sz, ci = ctypes.c_size_t, ctypes.c_int
-    L.emu_plan_rows.argtypes = [ci, sz, sz, sz, ctypes.POINTER(ctypes.c_uint32)]
-    L.emu_row_policy.argtypes = [ci, ci]; L.emu_row_policy.restype = ctypes.c_long
     resident = 4 * torch.cuda.get_device_properties(0).multi_processor_count
-    chunk = ctypes.c_uint32()
 
     def smallest_dynamic(row_bytes):
-        want = max(1, -(-L.emu_row_policy(0, 0) // row_bytes))
-        rows = L.emu_row_policy(0, 1) * resident * want
-        assert L.emu_plan_rows(0, row_bytes, rows, resident, ctypes.byref(chunk)) == 1 and chunk.value == want
-        assert L.emu_plan_rows(0, row_bytes, rows - 1, resident, ctypes.byref(chunk)) == 0
-        return rows
+        return smallest_dynamic_batch(row_bytes, resident)
 
     rows = smallest_dynamic(terms * n * plan.elem_bytes)
     a = plan.fill_lcg(rows * terms, 1, 2); b = plan.fill_lcg(rows * terms, 2, 2)

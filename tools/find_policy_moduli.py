@@ -12,7 +12,15 @@ By default a boundary is found by bisection over the primes between 2^(k-1) and 
 flag which holds for the largest prime below 2^k holds for every prime down to the boundary: every bound the schedules check
 grows with c = 2^k - q.  --walk visits every NTT prime from 2^k downwards instead and needs no such assumption (minutes per
 pair at n = 256 for k = 59 and 60).  Both found the same pairs when the table was made.
-tests/test_policy_moduli_emu.py::test_table_flags_and_boundary_pairs re-checks every literal in one prime step per pair."""
+tests/test_policy_moduli_emu.py::test_table_flags_and_boundary_pairs re-checks every literal in one prime step per pair.
+
+--tables flags prints the tables of the other replays instead (--tables all, the default, prints both): for n = 4096 and every k
+of K_BOUNDARY the boundaries of cg_lazy, cg_sched and cin (HostTables' flags, asked through emu_plan_flags) where they are not
+the lazy pair itself, as CG_PAIRS and CIN_PAIRS; the lazy boundaries of n = 512, 1024 and 2048 at k = 26 and 60 as MID_PAIRS;
+and FLAG_ENTRIES, all five flags of every prime of those pairs, of the n = 4096 lazy and bc pairs at k = 59 and 60 and of Q60.
+cg_sched has pairs of its own at k = 59 and 60 and cin at k = 60; cg_lazy has none, nor have cg_sched and cin at k <= 55.
+Bisection (3 s) and --walk (1 min) printed the same text when these tables were made, the cg_sched pairs at k = 59 and 60 and the
+cin pair at k = 60 among it.  tests/test_policy_flags_emu.py::test_flag_tables_and_boundary_pairs re-checks every literal."""
 import argparse
 import os
 import sys
@@ -29,12 +37,30 @@ Q23, Q60 = 8380417, 1152921504606830593
 REFERENCE = [(256, Q23), (4096, Q23), (4096, Q60), (8192, Q60)]
 
 
+FLAG_NAMES = ("lazy", "cg_lazy", "cg_sched", "cin", "bc")          # bit order of emu_plan_flags (tests/emu/emu_kernels.cpp)
+MID_N, MID_K = (512, 1024, 2048), (26, 60)
+K_FLAGS = (59, 60)                                                  # word lengths whose n = 4096 lazy / bc pairs join FLAG_ENTRIES
+
+
 class Flags:
     def __init__(self):
         import ctypes
         self.lib = Emu().lib
         self.lib.bc_enabled.argtypes = [ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64]
-        self.cache = {}
+        self.lib.emu_plan_flags.argtypes = [ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64]
+        self.cache, self.masks = {}, {}
+
+    def mask(self, n, q):
+        """(lazy, cg_lazy, cg_sched, cin, bc) of the plan (n, q): HostTables' own flags, through emu_plan_flags."""
+        if (n, q) not in self.masks:
+            m = self.lib.emu_plan_flags(n, q, numtheory.primitive_2n_root(n, q))
+            assert 0 <= m < 32, (n, q, m)
+            self.masks[(n, q)] = tuple(bool(m >> i & 1) for i in range(len(FLAG_NAMES)))
+        return self.masks[(n, q)]
+
+    def has(self, name):
+        which = FLAG_NAMES.index(name)
+        return lambda n, q: self.mask(n, q)[which]
 
     def __call__(self, n, q):
         """(lazy, bc) of the plan (n, q)."""
@@ -97,12 +123,57 @@ def boundary(flag, n, k, walk):
             bad = q
 
 
+def flag_tables(flags, walk):
+    """CG_PAIRS, CIN_PAIRS, MID_PAIRS and FLAG_ENTRIES.  A flag whose boundary is the lazy policy's at that word length has no pair
+    of its own (cg_lazy everywhere; cg_sched and cin at k <= 55): the self-check asserts that it equals lazy there."""
+    n = 4096
+    tables = {"cg_lazy": [], "cg_sched": [], "cin": []}
+    entries = {(n, Q60)}
+    for k in K_BOUNDARY:
+        lazy = boundary(flags.has("lazy"), n, k, walk)
+        for name, found in tables.items():
+            pair = boundary(flags.has(name), n, k, walk)
+            if pair is None:                         # 32-bit lanes (or no lazy prime of k bits): the flag is never set
+                assert lazy is None or not any(flags.has(name)(n, q) for q in lazy), (name, k)
+            elif pair != lazy:
+                found.append((n, name) + pair)
+                entries.update((n, q) for q in pair)
+        if k in K_FLAGS:
+            entries.update((n, q) for q in lazy + boundary(flags.has("bc"), n, k, walk))
+    assert not tables["cg_lazy"], tables["cg_lazy"]          # never tighter than lazy with 64-bit lanes
+    mid = []
+    for m in MID_N:
+        for k in MID_K:
+            pair = boundary(flags.has("lazy"), m, k, walk)
+            mid.append((m, "lazy") + pair)
+            entries.update((m, q) for q in pair)
+    for name, rows in (("CG_PAIRS", tables["cg_sched"]), ("CIN_PAIRS", tables["cin"]), ("MID_PAIRS", mid)):
+        print(f"{name} = [")
+        for p in rows:
+            print(f"    ({p[0]}, \"{p[1]}\", {p[2]}, {p[3]}),")
+        print("]")
+    print("# (n, q, " + ", ".join(FLAG_NAMES) + ")")
+    print("FLAG_ENTRIES = [")
+    for n_, q in sorted(entries):
+        print(f"    ({n_}, {q}, " + ", ".join(str(f) for f in flags.mask(n_, q)) + "),")
+    print("]")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--n", type=int, nargs="+", default=[256, 4096, 8192])
     ap.add_argument("--walk", action="store_true", help="visit every NTT prime from 2^k downwards instead of bisecting")
+    ap.add_argument("--tables", choices=("all", "policy", "flags"), default="all",
+                    help="policy: PAIRS and ENTRIES; flags: CG_PAIRS, CIN_PAIRS, MID_PAIRS and FLAG_ENTRIES (n = 512 ... 4096, whatever --n says)")
     args = ap.parse_args()
     flags = Flags()
+    if args.tables != "flags":
+        policy_tables(flags, args)
+    if args.tables != "policy":
+        flag_tables(flags, args.walk)
+
+
+def policy_tables(flags, args):
     pairs, entries = [], []
 
     def add(n, q):
