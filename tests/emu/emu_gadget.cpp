@@ -8,7 +8,7 @@
 
 namespace {
 
-// what tn_gadget_decompose_dev / tn_poly_gadget_dot_prepared_dev refuse (capi.cpp: check_gadget)
+// what tn_gadget_decompose_dev / tn_poly_gadget_dot_prepared_dev refuse (csrc/api_checks.h: ApiCheck::gadget)
 bool gadget_ok(u64 q, size_t terms, u32 base_log, u32 flags) {
   if (terms == 0 || (flags & ~1u)) return false;
   if (base_log == 0 || base_log >= 64 || (((u64)1) << base_log) >= q) return false;

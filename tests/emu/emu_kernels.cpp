@@ -2,12 +2,14 @@
 // constant-geometry kernels (tiny_ntt_amd/csrc/fused_core.h, cg_core.h, modarith.h, plan_tables.h — the very headers the
 // gfx950 kernels are compiled from) on the CPU, one emulated thread at a time with barriers between phases, so index maps,
 // LDS layouts, table semantics and lazy-reduction bounds can be checked without a GPU; also the layout, schedule and
-// arithmetic probes.  The fused shape, tables and constants of a launch and the row planning come from launch_plan.h, the
+// arithmetic probes, and the entry points' argument checks (csrc/api_checks.h: emu_api_check).  The fused shape, tables and constants of a launch and the row planning come from launch_plan.h, the
 // header the launchers take them from (the Stepper and emu_with_shape: emu_stepper.h).  One of the five objects of
 // tests/emu/_build/libemu.so (tests/emu/Makefile); loaded by tests/conftest.py (Emu).  It is not a product path and nothing in
 // tiny_ntt_amd/ loads it.
 #include "emu_stepper.h"
 #include "../../tiny_ntt_amd/csrc/cg_core.h"
+#include "../../tiny_ntt_amd/csrc/api_checks.h"
+#include <cstdio>
 
 namespace {
 
@@ -432,5 +434,34 @@ long emu_split_sched_stat(int logn, int what) {
   return with_fused_shape(8, true, (u32)logn, -1L, [&](auto sh) { return stat(typename decltype(sh)::Cfg()); });
 }
 uint32_t emu_fold32(uint32_t x, uint32_t q) { const int k = h_bitlen(q); return fold(x, k, (u32)((((u64)1) << k) - q)); }
+
+// The argument checks of the device entry point `entry` (api_checks.h: the step list capi.cpp runs before its launch) on a plan
+// view made of (n, elem_bytes, has_fused, omega_only, q); n == 0 is a NULL plan.  a, b: the inputs in the order of the C
+// signature (b unused where there is one); out: the output; sets: bhat_rows / bhat_sets.  Returns the status, or -1 for an
+// unknown entry; *launch = 1 when the call would go on to its launch; msg receives the text tn_last_error would give.
+int emu_api_check(const char* entry, uint32_t n, int elem_bytes, int has_fused, int omega_only, uint64_t q, const void* a, const void* b,
+                  const void* out, size_t sets, size_t batch, size_t terms, int out_prepared, uint32_t base_log, uint32_t flags, int* launch,
+                  char* msg, size_t msg_len) {
+  ApiCheck k{ApiPlan{n, elem_bytes, has_fused != 0, omega_only != 0, q}, entry};
+  const std::string e = entry;
+  bool go;
+  if (e == "tn_poly_mult_dev" || e == "tn_cyclic_poly_mult_dev") go = check_product(k, a, b, out, batch, e == "tn_cyclic_poly_mult_dev");
+  else if (e == "tn_ntt_forward_dev" || e == "tn_ntt_inverse_dev" || e == "tn_twisted_ntt_forward_dev")
+    go = check_transform(k, a, out, batch, e == "tn_twisted_ntt_forward_dev");
+  else if (e == "tn_prepare_dev" || e == "tn_unprepare_dev") go = check_prepare(k, a, out, batch);
+  else if (e == "tn_schoolbook_dev") go = check_rows(k, a, b, out, batch);
+  else if (e == "tn_pointwise_mul_dev") go = check_pointwise(k, a, b, out, batch);
+  else if (e == "tn_poly_mult_prepared_dev") go = check_mult_prepared(k, a, b, sets, out, batch);
+  else if (e == "tn_poly_dot_prepared_dev") go = check_dot(k, a, b, sets, out, batch, terms, 0, "rows of a");
+  else if (e == "tn_poly_dot_hat_dev") go = check_dot(k, a, b, sets, out, batch, terms, out_prepared, "rows of ahat");
+  else if (e == "tn_gadget_decompose_dev") go = check_gadget_decompose(k, a, out, batch, terms, base_log, flags);
+  else if (e == "tn_poly_gadget_dot_prepared_dev") go = check_gadget_dot(k, a, b, sets, out, batch, terms, base_log, flags);
+  else if (e == "tn_fill_lcg_dev") go = check_fill(k, out != nullptr, batch);
+  else if (e == "tn_checksum_rows_dev") go = check_fill(k, a && out, batch);
+  else return -1;
+  if (launch) *launch = go ? 1 : 0;
+  if (msg && msg_len) std::snprintf(msg, msg_len, "%s", k.msg.c_str());
+  return (int)k.st;
+}
 
 }  // extern "C"

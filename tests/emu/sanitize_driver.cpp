@@ -27,6 +27,9 @@ int emu_poly_gadget_dot_prepared(uint32_t n, uint64_t q, uint64_t psi, int canon
                                  uint64_t* c, size_t batch, size_t terms, uint32_t base_log, uint32_t flags);
 int emu_gadget_digits(uint32_t n, uint64_t q, uint64_t psi, int canonical, const uint64_t* x, uint64_t* digits, size_t count, size_t terms,
                       uint32_t base_log, uint32_t flags, int* lane_bytes, int* lazy);
+int emu_api_check(const char* entry, uint32_t n, int elem_bytes, int has_fused, int omega_only, uint64_t q, const void* a, const void* b,
+                  const void* out, size_t sets, size_t batch, size_t terms, int out_prepared, uint32_t base_log, uint32_t flags, int* launch,
+                  char* msg, size_t msg_len);
 }
 
 namespace {
@@ -125,6 +128,52 @@ void family_cases(const P& p) {
     }
   }
 }
+
+// The argument checks of the entry points (csrc/api_checks.h) on made-up addresses: the overlap rows of tests/api_cases.py as a
+// sweep at the smallest plan (n = 4, 4-byte words) with the input 4 rows above address 8, against the intersection of the byte
+// ranges counted byte by byte; and its row-limit rows, (3, 2^63) at address 4096 among them.  Address arithmetic that wraps or
+// leaves the object a pointer came from would be reported here.
+void api_check_cases() {
+  const uint32_t n = 4;
+  const uintptr_t row = n * 4, base = 4 * row + 8, far = (uintptr_t)1 << 40;
+  auto at = [](uintptr_t x) { return (const void*)x; };
+  auto meet = [](uintptr_t x, size_t xb, uintptr_t y, size_t yb) {
+    for (uintptr_t i = x; i < x + xb; ++i) if (i >= y && i < y + yb) return true;
+    return false;
+  };
+  struct Shape { const char* entry; int shared, out_terms, a_terms, b_terms; };      // rows = batch * (terms or 1); b_terms -1: no b
+  const Shape shapes[] = {{"tn_poly_mult_dev", 0, 0, 0, 0}, {"tn_ntt_forward_dev", 0, 0, 0, -1}, {"tn_unprepare_dev", 0, 0, 0, -1},
+                          {"tn_gadget_decompose_dev", 0, 1, 0, -1}, {"tn_poly_mult_prepared_dev", 0, 0, 0, 0}, {"tn_poly_mult_prepared_dev", 1, 0, 0, 0},
+                          {"tn_poly_dot_prepared_dev", 0, 0, 1, 1}, {"tn_poly_dot_prepared_dev", 1, 0, 1, 1}, {"tn_poly_dot_hat_dev", 0, 0, 1, 1},
+                          {"tn_poly_dot_hat_dev", 1, 0, 1, 1}, {"tn_poly_gadget_dot_prepared_dev", 0, 0, 0, 1}, {"tn_poly_gadget_dot_prepared_dev", 1, 0, 0, 1}};
+  for (const Shape& sh : shapes)
+    for (size_t batch = 1; batch <= 3; ++batch) for (size_t terms = 1; terms <= 3; ++terms) for (int which = 0; which < (sh.b_terms < 0 ? 1 : 2); ++which) {
+      const size_t out_rows = batch * (sh.out_terms ? terms : 1);
+      const bool mult = std::strcmp(sh.entry, "tn_poly_mult_prepared_dev") == 0;
+      const size_t in_rows = which == 0 ? batch * (sh.a_terms ? terms : 1) : (sh.shared ? 1 : batch) * (sh.b_terms && !mult ? terms : 1);
+      bool ok = true;
+      for (int off = -4; off <= 7; ++off) {
+        const uintptr_t out = base + (uintptr_t)((intptr_t)off * (intptr_t)row);
+        int launch = -1;
+        const int st = emu_api_check(sh.entry, n, 4, 1, 0, 7681, at(which == 0 ? base : far), at(which == 0 ? far : base), at(out), sh.shared ? 1 : batch, batch,
+                                     terms, 0, 4, 0, &launch, nullptr, 0);
+        const bool want = meet(out, out_rows * row, base, in_rows * row);
+        ok = ok && st == (want ? 6 : 0) && launch == (want ? 0 : 1);
+      }
+      expect(ok, sh.entry, n, sh.shared, (int)batch, (int)terms, which);
+    }
+  const size_t M = (size_t)1 << 31;
+  const size_t pairs[][2] = {{M - 2, 1}, {M - 1, 1}, {M, 1}, {1, M - 2}, {1, M - 1}, {1, M}, {(size_t)1 << 16, (size_t)1 << 15}, {(size_t)1 << 15, ((size_t)1 << 16) - 1},
+                             {(size_t)1 << 30, 2}, {3, (size_t)1 << 63}};
+  for (const char* entry : {"tn_poly_dot_prepared_dev", "tn_poly_dot_hat_dev"})
+    for (const auto& pr : pairs) {
+      const bool fits = pr[0] <= M - 1 && pr[1] <= M - 1 && pr[0] * pr[1] <= M - 1;          // (no wrap: both factors are below 2^31 here)
+      const bool dummy = !fits;                                                              // refused rows: every pointer at address 4096
+      const int st = emu_api_check(entry, n, 4, 1, 0, 7681, at(dummy ? 4096 : (uintptr_t)1 << 44), at(dummy ? 4096 : (uintptr_t)1 << 48),
+                                   at(dummy ? 4096 : (uintptr_t)1 << 52), 1, pr[0], pr[1], 0, 0, 0, nullptr, nullptr, 0);
+      expect(st == (fits ? 0 : 6), entry, n, (int)(pr[0] >> 16), (int)(pr[1] >> 16), st, 0);
+    }
+}
 }  // namespace
 
 int main() {
@@ -188,6 +237,7 @@ int main() {
   // the four later families at their smallest shapes: 32-bit lanes, 64-bit lanes, and the one base-case shape
   for (const P& p : sets)
     if ((p.n == 256) || (p.n == base60.n && p.q == base60.q)) family_cases(p);
+  api_check_cases();
   std::printf("sanitize_driver: %zu parameter sets, %d checks, %d failures\n", sets.size(), checks, failures);
   return failures ? 1 : 0;
 }

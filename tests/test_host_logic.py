@@ -37,7 +37,7 @@ def test_build_id_names_the_sources_the_library_was_built_from():
     d = os.path.join(ROOT, "tiny_ntt_amd", "csrc")
     files = ["kernels.hip", "kernels_prepared.hip", "kernels_hat.hip", "kernels_gadget.hip", "cg_part.hip", "capi.cpp", "multi.cpp", "modarith.h", "fused_core.h",
              "fused_kernels.h", "launch_plan.h", "cg_core.h", "cg_kernel_impl.h", "dev_addr.h", "plan.h",
-             "plan_tables.h", "../../include/tinyntt.h"]        # the order of csrc/Makefile: BUILD_ID
+             "plan_tables.h", "api_checks.h", "../../include/tinyntt.h"]        # the order of csrc/Makefile: BUILD_ID
     h = hashlib.sha256(b"".join(open(os.path.join(d, f), "rb").read() for f in files)).hexdigest()[:16]
     assert engine.build_id() == h, "tiny_ntt_amd/lib/libtinyntt.so is stale: run make -C tiny_ntt_amd/csrc"
 
@@ -211,3 +211,28 @@ def test_host_rows_take_integers_mod_q_and_refuse_floats():
         f(P(), [1.5, 2, 3, 4], "a")
     with pytest.raises(ValueError):
         f(P(), [1, 2, 3], "a")
+
+
+def test_prepared_operand_sets_rule_and_ownership():
+    """The helpers the prepared family shares (no device needed): Plan._sets is the "one set or one per row" rule, and
+    Plan._own_prepared the only judge of a PreparedOperand."""
+    class P:                                            # stand-in: only identity matters to _own_prepared
+        pass
+    plan, other = P(), P()
+    operand = lambda rows, owner=plan: engine.PreparedOperand(owner, None, rows)
+    sets = engine.Plan._sets
+    assert sets(operand(2), 5, 2) == 1                  # `terms` rows: one set for every output row
+    assert sets(operand(10), 5, 2) == 5                 # batch * terms rows: a set per row
+    with pytest.raises(ValueError, match="Expected a prepared operand of 2 or 10 rows, got 3"):
+        sets(operand(3), 5, 2)
+    with pytest.raises(ValueError, match="Expected a second operand of 2 or 10 rows, got 3"):
+        sets(operand(3), 5, 2, "second operand")
+    assert sets(operand(2), 1, 2) == 1                  # batch 1: both readings agree, and the C ABI takes 1 either way
+    own = engine.Plan._own_prepared
+    assert own(plan, operand(2), "poly_mult_prepared", "second operand") is None
+    with pytest.raises(engine.TinyNttError, match="poly_dot_prepared: the prepared operand belongs to another plan") as e:
+        own(plan, operand(2, other), "poly_dot_prepared", "second operand")
+    assert e.value.status == engine.TN_EINVAL
+    for not_prepared in (np.zeros((2, 4), dtype=np.uint32), None, [1, 2, 3, 4]):
+        with pytest.raises(TypeError, match="unprepare: the operand must come from Plan.prepare"):
+            own(plan, not_prepared, "unprepare", "operand")

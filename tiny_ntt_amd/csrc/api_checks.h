@@ -1,0 +1,121 @@
+// api_checks.h — the argument checks of the device entry points (capi.cpp), free of HIP: arithmetic on a small view of the
+// plan and on the call's sizes and pointers, so tests/emu runs them on the CPU.  A step returns true when the call goes on;
+// when it returns false, st and msg are the call's answer (st == TN_OK: nothing to do).  Each entry point is one ordered
+// list of steps below; that order is behaviour of the C ABI: it decides which status and text a call with several faults gets.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+#include <string>
+#include "../../include/tinyntt.h"
+
+namespace tn {
+
+struct ApiPlan { uint32_t n; int elem_bytes; bool has_fused, omega_only; uint64_t q; };     // a NULL plan: n == 0
+
+struct KernelPick { bool known, fused; int group, layout; };     // layout: CgLayout, cg_core.h (0 linear, 1 padded, 2 swizzled)
+// The kernel a variant names; TN_VARIANT_AUTO is the fused kernel where the plan has it (and no trace is wanted), else CG.
+static inline KernelPick pick_kernel(const ApiPlan& v, tn_variant variant, bool trace = false) {
+  static const signed char cg[][2] = {{1, 0}, {8, 0}, {8, 1}, {1, 2}, {8, 2}, {2, 0}, {2, 1}, {2, 2}, {4, 0}, {4, 1}, {4, 2}};   // TN_VARIANT_CG ...
+  if (variant == TN_VARIANT_AUTO) variant = (v.has_fused && !trace) ? TN_VARIANT_FUSED : TN_VARIANT_CG;
+  if (variant == TN_VARIANT_FUSED) return {true, true, 0, 0};
+  if (variant < TN_VARIANT_CG || variant > TN_VARIANT_CG4_SWIZZLED) return {false, false, 0, 0};
+  return {true, false, cg[variant - TN_VARIANT_CG][0], cg[variant - TN_VARIANT_CG][1]};
+}
+
+struct __attribute__((visibility("hidden"))) ApiCheck {          // (hidden, static: the library exports the C ABI alone)
+  ApiPlan v;
+  const char* fn;
+  tn_status st = TN_OK;
+  std::string msg;
+  ApiCheck(const ApiPlan& view, const char* name) : v(view), fn(name) {}
+  bool fail(tn_status s, const char* what, bool named = true) {
+    st = s; msg = named ? std::string(fn) + ": " + what : std::string(what);
+    return false;
+  }
+  bool plan() { return v.n || fail(TN_EINVAL, "plan is NULL"); }
+  bool arguments(bool present) { return present || fail(TN_EINVAL, "NULL argument"); }
+  bool fused() { return v.has_fused || fail(TN_EUNSUPPORTED, "prepared operands need a plan with the fused kernels (tn_plan_has_fused)"); }
+  bool psi(const char* why) { return !v.omega_only || fail(TN_EUNSUPPORTED, why); }
+  bool terms(size_t terms) { return terms || fail(TN_EINVAL, "terms must be at least 1"); }
+  // the kernels index rows with 32 bits; the division keeps batch * terms from wrapping size_t first
+  bool rows(size_t batch, size_t terms, const char* count, const char* noun) {
+    const size_t max = 0x7fffffffull;
+    return !(batch > max || terms > max || (batch && terms > max / batch)) ||
+           fail(TN_EINVAL, (std::string(count) + " too large for one call (max 2^31 - 1 " + noun + ")").c_str());
+  }
+  bool rows_wide(size_t batch) { return batch <= 0xffffffffull || fail(TN_EINVAL, "batch too large"); }      // grid-stride kernels
+  bool work(size_t batch) { return batch != 0; }                                              // batch 0: TN_OK, nothing launched
+  bool buffers(bool present) { return present || fail(TN_EINVAL, "NULL buffer"); }
+  bool sets(size_t sets, size_t batch, const char* name, const char* one) {
+    return sets == 1 || sets == batch || fail(TN_EINVAL, (std::string(name) + " must be 1 (" + one + ") or batch").c_str());
+  }
+  bool out_prepared(int flag) { return flag == 0 || flag == 1 || fail(TN_EINVAL, "out_prepared must be 0 (coefficients) or 1 (prepared rows)"); }
+  // what both gadget calls ask: terms >= 1, known flags, 0 < base_log, 2^base_log < q, no shift reaches the word width
+  bool gadget(size_t batch, size_t terms_, uint32_t base_log, uint32_t flags) {
+    if (!terms(terms_)) return false;
+    if (flags & ~(uint32_t)TN_GADGET_BALANCED) return fail(TN_EINVAL, "unknown flag bit");
+    if (base_log == 0 || base_log >= 64 || (((uint64_t)1) << base_log) >= v.q) return fail(TN_EINVAL, "need 1 <= base_log and 2^base_log < q");
+    if (terms_ - 1 > 63 / base_log) return fail(TN_EINVAL, "(terms - 1) * base_log must be below 64");
+    return rows(batch, terms_, "batch * terms", "digit rows");
+  }
+  // The byte ranges of out_rows rows at out and in_rows rows at in share no byte: the kernels prefetch the next row's input
+  // while a row's result is being stored.  Compared as integers: a caller may pass any address, also one near 0.
+  bool apart(const void* out, size_t out_rows, const void* in, size_t in_rows, const char* noun) {
+    const uintptr_t o = (uintptr_t)out, i = (uintptr_t)in, row = (uintptr_t)v.n * (uintptr_t)v.elem_bytes;
+    return !(o < i + in_rows * row && i < o + out_rows * row) || fail(TN_EINVAL, (std::string("output must not alias or overlap ") + noun).c_str());
+  }
+  // tn_poly_mult_dev words these two without its name (named = false)
+  bool kernel(const KernelPick& k, bool trace, bool named = true) {
+    if (!k.known) return fail(TN_EINVAL, "unknown variant", named);
+    if (k.fused && !v.has_fused) return fail(TN_EUNSUPPORTED, "fused kernel not built for this n; use TN_VARIANT_CG", named);
+    // register-tiled kernel: same results, no per-stage trace (its internal stages are not the CG stages)
+    return !(k.fused && trace) || fail(TN_EUNSUPPORTED, "per-stage traces need a CG variant");
+  }
+};
+
+// ---- one list per entry point (entry points with the same list share it) ----------------------
+// c = f(a, b) row by row, or out = f(in) given as a == b: schoolbook, the *_host calls, and the head of the next three
+static inline bool check_rows(ApiCheck& k, const void* a, const void* b, const void* c, size_t batch) {
+  return k.plan() && k.rows(batch, 1, "batch", "rows") && k.buffers(!batch || (a && b && c)) &&
+         k.apart(c, batch, a, batch, "an input") && k.apart(c, batch, b, batch, "an input");
+}
+static inline bool check_product(ApiCheck& k, const void* a, const void* b, const void* c, size_t batch, bool cyclic) {
+  return check_rows(k, a, b, c, batch) &&
+         k.psi(cyclic ? "not available on an omega-only plan" : "an omega-only plan has no psi (tn_plan_create_omega offers cg_ntt / cg_intt only)");
+}
+static inline bool check_transform(ApiCheck& k, const void* in, const void* out, size_t batch, bool twist) {
+  return check_rows(k, in, in, out, batch) && (!twist || k.psi("an omega-only plan has no psi to twist with"));
+}
+static inline bool check_prepare(ApiCheck& k, const void* in, const void* out, size_t rows) {            // and tn_unprepare_dev
+  return check_rows(k, in, in, out, rows) && k.fused();
+}
+static inline bool check_mult_prepared(ApiCheck& k, const void* a, const void* bhat, size_t bhat_rows, const void* c, size_t batch) {
+  return k.plan() && k.fused() && k.rows(batch, 1, "batch", "rows") && k.work(batch) && k.buffers(a && bhat && c) &&
+         k.sets(bhat_rows, batch, "bhat_rows", "shared operand") && k.apart(c, batch, a, batch, "an input") &&
+         k.apart(c, batch, bhat, bhat_rows, "an input");
+}
+// tn_poly_dot_prepared_dev (out_prepared 0, "rows of a") and tn_poly_dot_hat_dev ("rows of ahat")
+static inline bool check_dot(ApiCheck& k, const void* a, const void* bhat, size_t sets, const void* out, size_t batch, size_t terms,
+                      int out_prepared, const char* noun) {
+  return k.plan() && k.fused() && k.terms(terms) && k.out_prepared(out_prepared) && k.rows(batch, terms, "batch * terms", noun) &&
+         k.work(batch) && k.buffers(a && bhat && out) && k.sets(sets, batch, "bhat_sets", "one set of operands for every row") &&
+         k.apart(out, batch, a, batch * terms, "an input") && k.apart(out, batch, bhat, sets * terms, "an input");
+}
+static inline bool check_gadget_decompose(ApiCheck& k, const void* a, const void* digits, size_t batch, size_t terms, uint32_t base_log, uint32_t flags) {
+  return k.plan() && k.gadget(batch, terms, base_log, flags) && k.work(batch) && k.buffers(a && digits) &&
+         k.apart(digits, batch * terms, a, batch, "the input");
+}
+static inline bool check_gadget_dot(ApiCheck& k, const void* a, const void* bhat, size_t sets, const void* c, size_t batch, size_t terms,
+                             uint32_t base_log, uint32_t flags) {
+  return k.plan() && k.fused() && k.gadget(batch, terms, base_log, flags) && k.work(batch) && k.buffers(a && bhat && c) &&
+         k.sets(sets, batch, "bhat_sets", "one set of operands for every row") && k.apart(c, batch, a, batch, "an input") &&
+         k.apart(c, batch, bhat, sets * terms, "an input");
+}
+static inline bool check_pointwise(ApiCheck& k, const void* a, const void* b, const void* c, size_t batch) {      // in place is allowed
+  return k.plan() && k.rows_wide(batch) && k.buffers(!batch || (a && b && c));
+}
+static inline bool check_fill(ApiCheck& k, bool buffers, size_t batch) {                          // tn_fill_lcg_dev, tn_checksum_rows_dev
+  return k.arguments(k.v.n && (!batch || buffers)) && k.rows_wide(batch);
+}
+
+}  // namespace tn

@@ -11,6 +11,7 @@
 #include "../../include/tinyntt.h"
 #include "plan.h"
 #include "plan_tables.h"
+#include "api_checks.h"
 
 using namespace tn;
 
@@ -179,84 +180,41 @@ extern "C" int tn_plan_is_general(const tn_plan* p) { return p && p->general && 
 
 static hipStream_t pick_stream(tn_plan* p, void* stream) { return stream ? (hipStream_t)stream : p->stream; }
 
-struct CgSel { int group; int layout; };     // layout: CgLayout, cg_core.h (0 linear, 1 padded, 2 swizzled)
-static bool cg_sel(tn_variant v, CgSel* s) {
-  switch (v) {
-    case TN_VARIANT_CG: *s = {1, 0}; return true;
-    case TN_VARIANT_CG8: *s = {8, 0}; return true;
-    case TN_VARIANT_CG8_PADDED: *s = {8, 1}; return true;
-    case TN_VARIANT_CG_SWIZZLED: *s = {1, 2}; return true;
-    case TN_VARIANT_CG8_SWIZZLED: *s = {8, 2}; return true;
-    case TN_VARIANT_CG2: *s = {2, 0}; return true;
-    case TN_VARIANT_CG2_PADDED: *s = {2, 1}; return true;
-    case TN_VARIANT_CG2_SWIZZLED: *s = {2, 2}; return true;
-    case TN_VARIANT_CG4: *s = {4, 0}; return true;
-    case TN_VARIANT_CG4_PADDED: *s = {4, 1}; return true;
-    case TN_VARIANT_CG4_SWIZZLED: *s = {4, 2}; return true;
-    default: return false;
-  }
+// ---- the device entry points: the argument checks (api_checks.h: an ordered list of steps per entry point), then the launch ----
+static ApiPlan view(const tn_plan* p) { return p ? ApiPlan{p->n, p->elem_bytes, p->has_fused, p->omega_only, p->q} : ApiPlan{}; }
+static tn_status refused(const ApiCheck& k) {          // the answer of a list that stopped; TN_OK when there was nothing to do
+  if (k.st) g_err = k.msg;
+  return k.st;
+}
+#define TN_CHECK(fn, list) ApiCheck k{view(p), fn}; if (!(list)) return refused(k)
+// check_rows alone, for the *_host calls and the timing helper: they go on through a *_dev call that checks the rest
+static tn_status rows_checked(const tn_plan* p, const void* a, const void* b, const void* c, size_t batch, const char* fn) {
+  ApiCheck k{view(p), fn};
+  check_rows(k, a, b, c, batch);
+  return refused(k);
 }
 
-static tn_status check_ptrs(const tn_plan* p, const void* a, const void* b, const void* c, size_t batch, const char* fn) {
-  if (!p) return fail(TN_EINVAL, std::string(fn) + ": plan is NULL");
-  if (batch > 0x7fffffffull) return fail(TN_EINVAL, std::string(fn) + ": batch too large for one call (max 2^31 - 1 rows)");
-  if (batch && (!a || !b || !c)) return fail(TN_EINVAL, std::string(fn) + ": NULL buffer");
-  if (batch) {                        // byte ranges: the kernels prefetch the next row's input while a row's result is being stored
-    const size_t bytes = batch * (size_t)p->n * (size_t)p->elem_bytes;
-    const char *ca = (const char*)a, *cb = (const char*)b, *cc = (const char*)c;
-    if ((cc < ca + bytes && ca < cc + bytes) || (cc < cb + bytes && cb < cc + bytes))
-      return fail(TN_EINVAL, std::string(fn) + ": output must not alias or overlap an input");
-  }
-  return TN_OK;
-}
-
-extern "C" tn_status tn_poly_mult_dev(tn_plan* p, const void* a, const void* b, void* c, size_t batch, tn_variant variant,
-                                      void* stream) {
-  tn_status st = check_ptrs(p, a, b, c, batch, "tn_poly_mult_dev");
-  if (st) return st;
-  if (p->omega_only) return fail(TN_EUNSUPPORTED, "tn_poly_mult_dev: an omega-only plan has no psi (tn_plan_create_omega offers cg_ntt / cg_intt only)");
+// tn_poly_mult_dev (CG_POLYMUL) and tn_cyclic_poly_mult_dev (CG_CYCLIC_POLYMUL)
+static tn_status product_dev(tn_plan* p, int mode, const void* a, const void* b, void* c, size_t batch, tn_variant variant, void* stream, const char* fn) {
+  const bool cyclic = mode == CG_CYCLIC_POLYMUL;
+  TN_CHECK(fn, check_product(k, a, b, c, batch, cyclic));
   TN_ON_DEVICE(p);
-  hipStream_t s = pick_stream(p, stream);
-  if (variant == TN_VARIANT_AUTO) variant = p->has_fused ? TN_VARIANT_FUSED : TN_VARIANT_CG;
-  if (variant == TN_VARIANT_FUSED) {
-    if (!p->has_fused) return fail(TN_EUNSUPPORTED, "fused kernel not built for this n; use TN_VARIANT_CG");
-    TN_HIP(launch_polymul_fused(p, a, b, c, batch, s));
-    return TN_OK;
-  }
-  CgSel sel;
-  if (!cg_sel(variant, &sel)) return fail(TN_EINVAL, "unknown variant");
-  TN_HIP(launch_cg(p, CG_POLYMUL, sel.group, sel.layout, a, b, c, nullptr, batch, s));
+  const KernelPick sel = pick_kernel(k.v, variant);
+  if (!k.kernel(sel, false, /*named=*/cyclic)) return refused(k);
+  if (sel.fused) TN_HIP(launch_polymul_fused(p, a, b, c, batch, pick_stream(p, stream), cyclic));
+  else TN_HIP(launch_cg(p, mode, sel.group, sel.layout, a, b, c, nullptr, batch, pick_stream(p, stream)));
   return TN_OK;
 }
-
-extern "C" tn_status tn_cyclic_poly_mult_dev(tn_plan* p, const void* a, const void* b, void* c, size_t batch, tn_variant variant,
-                                             void* stream) {
-  tn_status st = check_ptrs(p, a, b, c, batch, "tn_cyclic_poly_mult_dev");
-  if (st) return st;
-  if (p->omega_only) return fail(TN_EUNSUPPORTED, "tn_cyclic_poly_mult_dev: not available on an omega-only plan");
-  TN_ON_DEVICE(p);
-  if (variant == TN_VARIANT_AUTO) variant = p->has_fused ? TN_VARIANT_FUSED : TN_VARIANT_CG;
-  if (variant == TN_VARIANT_FUSED) {
-    if (!p->has_fused) return fail(TN_EUNSUPPORTED, "tn_cyclic_poly_mult_dev: fused kernel not built for this n; use TN_VARIANT_CG");
-    TN_HIP(launch_polymul_fused(p, a, b, c, batch, pick_stream(p, stream), /*cyclic=*/true));
-    return TN_OK;
-  }
-  CgSel sel;
-  if (!cg_sel(variant, &sel)) return fail(TN_EINVAL, "tn_cyclic_poly_mult_dev: unknown variant");
-  TN_HIP(launch_cg(p, CG_CYCLIC_POLYMUL, sel.group, sel.layout, a, b, c, nullptr, batch, pick_stream(p, stream)));
-  return TN_OK;
+extern "C" tn_status tn_poly_mult_dev(tn_plan* p, const void* a, const void* b, void* c, size_t batch, tn_variant variant, void* stream) {
+  return product_dev(p, CG_POLYMUL, a, b, c, batch, variant, stream, "tn_poly_mult_dev");
+}
+extern "C" tn_status tn_cyclic_poly_mult_dev(tn_plan* p, const void* a, const void* b, void* c, size_t batch, tn_variant variant, void* stream) {
+  return product_dev(p, CG_CYCLIC_POLYMUL, a, b, c, batch, variant, stream, "tn_cyclic_poly_mult_dev");
 }
 
 // ---- prepared operand ----------------------------------------------------------
-static bool ranges_overlap(const void* x, size_t xbytes, const void* y, size_t ybytes) {
-  const char *cx = (const char*)x, *cy = (const char*)y;
-  return cx < cy + ybytes && cy < cx + xbytes;
-}
-
 extern "C" tn_status tn_prepare_dev(tn_plan* p, const void* b, void* bhat, size_t rows, void* stream) {
-  tn_status st = check_ptrs(p, b, b, bhat, rows, "tn_prepare_dev");         // NULL plan / buffers, bhat overlapping b
-  if (st) return st;
-  if (!p->has_fused) return fail(TN_EUNSUPPORTED, "tn_prepare_dev: prepared operands need a plan with the fused kernels (tn_plan_has_fused)");
+  TN_CHECK("tn_prepare_dev", check_prepare(k, b, bhat, rows));
   TN_ON_DEVICE(p);
   TN_HIP(launch_prepare(p, b, bhat, rows, pick_stream(p, stream)));
   return TN_OK;
@@ -264,16 +222,7 @@ extern "C" tn_status tn_prepare_dev(tn_plan* p, const void* b, void* bhat, size_
 
 extern "C" tn_status tn_poly_mult_prepared_dev(tn_plan* p, const void* a, const void* bhat, size_t bhat_rows, void* c, size_t batch,
                                                void* stream) {
-  const char* fn = "tn_poly_mult_prepared_dev";
-  if (!p) return fail(TN_EINVAL, std::string(fn) + ": plan is NULL");
-  if (!p->has_fused) return fail(TN_EUNSUPPORTED, std::string(fn) + ": prepared operands need a plan with the fused kernels (tn_plan_has_fused)");
-  if (batch > 0x7fffffffull) return fail(TN_EINVAL, std::string(fn) + ": batch too large for one call (max 2^31 - 1 rows)");
-  if (batch == 0) return TN_OK;
-  if (!a || !bhat || !c) return fail(TN_EINVAL, std::string(fn) + ": NULL buffer");
-  if (bhat_rows != 1 && bhat_rows != batch) return fail(TN_EINVAL, std::string(fn) + ": bhat_rows must be 1 (shared operand) or batch");
-  const size_t row_bytes = (size_t)p->n * (size_t)p->elem_bytes;
-  if (ranges_overlap(c, batch * row_bytes, a, batch * row_bytes) || ranges_overlap(c, batch * row_bytes, bhat, bhat_rows * row_bytes))
-    return fail(TN_EINVAL, std::string(fn) + ": output must not alias or overlap an input");
+  TN_CHECK("tn_poly_mult_prepared_dev", check_mult_prepared(k, a, bhat, bhat_rows, c, batch));
   TN_ON_DEVICE(p);
   TN_HIP(launch_polymul_prepared(p, a, bhat, bhat_rows == 1, c, batch, pick_stream(p, stream)));
   return TN_OK;
@@ -281,19 +230,7 @@ extern "C" tn_status tn_poly_mult_prepared_dev(tn_plan* p, const void* a, const 
 
 extern "C" tn_status tn_poly_dot_prepared_dev(tn_plan* p, const void* a, const void* bhat, size_t bhat_sets, void* c, size_t batch,
                                               size_t terms, void* stream) {
-  const char* fn = "tn_poly_dot_prepared_dev";
-  if (!p) return fail(TN_EINVAL, std::string(fn) + ": plan is NULL");
-  if (!p->has_fused) return fail(TN_EUNSUPPORTED, std::string(fn) + ": prepared operands need a plan with the fused kernels (tn_plan_has_fused)");
-  if (terms == 0) return fail(TN_EINVAL, std::string(fn) + ": terms must be at least 1");
-  // (the kernel indexes rows of a with 32 bits; the division keeps batch * terms from wrapping size_t first)
-  if (batch > 0x7fffffffull || terms > 0x7fffffffull || (batch && terms > 0x7fffffffull / batch))
-    return fail(TN_EINVAL, std::string(fn) + ": batch * terms too large for one call (max 2^31 - 1 rows of a)");
-  if (batch == 0) return TN_OK;
-  if (!a || !bhat || !c) return fail(TN_EINVAL, std::string(fn) + ": NULL buffer");
-  if (bhat_sets != 1 && bhat_sets != batch) return fail(TN_EINVAL, std::string(fn) + ": bhat_sets must be 1 (one set of operands for every row) or batch");
-  const size_t row_bytes = (size_t)p->n * (size_t)p->elem_bytes;
-  if (ranges_overlap(c, batch * row_bytes, a, batch * terms * row_bytes) || ranges_overlap(c, batch * row_bytes, bhat, bhat_sets * terms * row_bytes))
-    return fail(TN_EINVAL, std::string(fn) + ": output must not alias or overlap an input");
+  TN_CHECK("tn_poly_dot_prepared_dev", check_dot(k, a, bhat, bhat_sets, c, batch, terms, 0, "rows of a"));
   TN_ON_DEVICE(p);
   TN_HIP(launch_polydot_prepared(p, a, bhat, bhat_sets == 1, c, batch, terms, pick_stream(p, stream)));
   return TN_OK;
@@ -301,9 +238,7 @@ extern "C" tn_status tn_poly_dot_prepared_dev(tn_plan* p, const void* a, const v
 
 // ---- transform domain: prepared rows in; coefficients or prepared rows out -----------
 extern "C" tn_status tn_unprepare_dev(tn_plan* p, const void* xhat, void* x, size_t rows, void* stream) {
-  tn_status st = check_ptrs(p, xhat, xhat, x, rows, "tn_unprepare_dev");     // NULL plan / buffers, x overlapping xhat
-  if (st) return st;
-  if (!p->has_fused) return fail(TN_EUNSUPPORTED, "tn_unprepare_dev: prepared operands need a plan with the fused kernels (tn_plan_has_fused)");
+  TN_CHECK("tn_unprepare_dev", check_prepare(k, xhat, x, rows));
   TN_ON_DEVICE(p);
   TN_HIP(launch_unprepare(p, xhat, x, rows, pick_stream(p, stream)));
   return TN_OK;
@@ -311,49 +246,16 @@ extern "C" tn_status tn_unprepare_dev(tn_plan* p, const void* xhat, void* x, siz
 
 extern "C" tn_status tn_poly_dot_hat_dev(tn_plan* p, const void* ahat, const void* bhat, size_t bhat_sets, void* out, size_t batch,
                                          size_t terms, int out_prepared, void* stream) {
-  const char* fn = "tn_poly_dot_hat_dev";
-  if (!p) return fail(TN_EINVAL, std::string(fn) + ": plan is NULL");
-  if (!p->has_fused) return fail(TN_EUNSUPPORTED, std::string(fn) + ": prepared operands need a plan with the fused kernels (tn_plan_has_fused)");
-  if (terms == 0) return fail(TN_EINVAL, std::string(fn) + ": terms must be at least 1");
-  if (out_prepared != 0 && out_prepared != 1) return fail(TN_EINVAL, std::string(fn) + ": out_prepared must be 0 (coefficients) or 1 (prepared rows)");
-  // (the kernel indexes rows of ahat with 32 bits; the division keeps batch * terms from wrapping size_t first)
-  if (batch > 0x7fffffffull || terms > 0x7fffffffull || (batch && terms > 0x7fffffffull / batch))
-    return fail(TN_EINVAL, std::string(fn) + ": batch * terms too large for one call (max 2^31 - 1 rows of ahat)");
-  if (batch == 0) return TN_OK;
-  if (!ahat || !bhat || !out) return fail(TN_EINVAL, std::string(fn) + ": NULL buffer");
-  if (bhat_sets != 1 && bhat_sets != batch) return fail(TN_EINVAL, std::string(fn) + ": bhat_sets must be 1 (one set of operands for every row) or batch");
-  const size_t row_bytes = (size_t)p->n * (size_t)p->elem_bytes;
-  if (ranges_overlap(out, batch * row_bytes, ahat, batch * terms * row_bytes) || ranges_overlap(out, batch * row_bytes, bhat, bhat_sets * terms * row_bytes))
-    return fail(TN_EINVAL, std::string(fn) + ": output must not alias or overlap an input");
+  TN_CHECK("tn_poly_dot_hat_dev", check_dot(k, ahat, bhat, bhat_sets, out, batch, terms, out_prepared, "rows of ahat"));
   TN_ON_DEVICE(p);
   TN_HIP(launch_polydot_hat(p, ahat, bhat, bhat_sets == 1, out, batch, terms, out_prepared == 1, pick_stream(p, stream)));
   return TN_OK;
 }
 
 // ---- gadget decomposition: digits of a, written out or cut inside the dot-product kernel -----------
-// the conditions both gadget calls share; 0 < base_log, 2^base_log < q, terms >= 1, no shift reaches the word width
-static tn_status check_gadget(const tn_plan* p, size_t batch, size_t terms, uint32_t base_log, uint32_t flags, const char* fn) {
-  if (terms == 0) return fail(TN_EINVAL, std::string(fn) + ": terms must be at least 1");
-  if (flags & ~(uint32_t)TN_GADGET_BALANCED) return fail(TN_EINVAL, std::string(fn) + ": unknown flag bit");
-  if (base_log == 0 || base_log >= 64 || (((u64)1) << base_log) >= p->q) return fail(TN_EINVAL, std::string(fn) + ": need 1 <= base_log and 2^base_log < q");
-  if (terms - 1 > 63 / base_log) return fail(TN_EINVAL, std::string(fn) + ": (terms - 1) * base_log must be below 64");
-  // (rows are indexed with 32 bits; the division keeps batch * terms from wrapping size_t first)
-  if (batch > 0x7fffffffull || (batch && terms > 0x7fffffffull / batch))
-    return fail(TN_EINVAL, std::string(fn) + ": batch * terms too large for one call (max 2^31 - 1 digit rows)");
-  return TN_OK;
-}
-
 extern "C" tn_status tn_gadget_decompose_dev(tn_plan* p, const void* a, void* digits, size_t batch, size_t terms, uint32_t base_log,
                                              uint32_t flags, void* stream) {
-  const char* fn = "tn_gadget_decompose_dev";
-  if (!p) return fail(TN_EINVAL, std::string(fn) + ": plan is NULL");
-  tn_status st = check_gadget(p, batch, terms, base_log, flags, fn);
-  if (st) return st;
-  if (batch == 0) return TN_OK;
-  if (!a || !digits) return fail(TN_EINVAL, std::string(fn) + ": NULL buffer");
-  const size_t row_bytes = (size_t)p->n * (size_t)p->elem_bytes;
-  if (ranges_overlap(digits, batch * terms * row_bytes, a, batch * row_bytes))
-    return fail(TN_EINVAL, std::string(fn) + ": output must not alias or overlap the input");
+  TN_CHECK("tn_gadget_decompose_dev", check_gadget_decompose(k, a, digits, batch, terms, base_log, flags));
   TN_ON_DEVICE(p);
   TN_HIP(launch_gadget_decompose(p, a, digits, batch, terms, base_log, (flags & TN_GADGET_BALANCED) != 0, pick_stream(p, stream)));
   return TN_OK;
@@ -361,34 +263,21 @@ extern "C" tn_status tn_gadget_decompose_dev(tn_plan* p, const void* a, void* di
 
 extern "C" tn_status tn_poly_gadget_dot_prepared_dev(tn_plan* p, const void* a, const void* bhat, size_t bhat_sets, void* c, size_t batch,
                                                      size_t terms, uint32_t base_log, uint32_t flags, void* stream) {
-  const char* fn = "tn_poly_gadget_dot_prepared_dev";
-  if (!p) return fail(TN_EINVAL, std::string(fn) + ": plan is NULL");
-  if (!p->has_fused) return fail(TN_EUNSUPPORTED, std::string(fn) + ": prepared operands need a plan with the fused kernels (tn_plan_has_fused)");
-  tn_status st = check_gadget(p, batch, terms, base_log, flags, fn);
-  if (st) return st;
-  if (batch == 0) return TN_OK;
-  if (!a || !bhat || !c) return fail(TN_EINVAL, std::string(fn) + ": NULL buffer");
-  if (bhat_sets != 1 && bhat_sets != batch) return fail(TN_EINVAL, std::string(fn) + ": bhat_sets must be 1 (one set of operands for every row) or batch");
-  const size_t row_bytes = (size_t)p->n * (size_t)p->elem_bytes;
-  if (ranges_overlap(c, batch * row_bytes, a, batch * row_bytes) || ranges_overlap(c, batch * row_bytes, bhat, bhat_sets * terms * row_bytes))
-    return fail(TN_EINVAL, std::string(fn) + ": output must not alias or overlap an input");
+  TN_CHECK("tn_poly_gadget_dot_prepared_dev", check_gadget_dot(k, a, bhat, bhat_sets, c, batch, terms, base_log, flags));
   TN_ON_DEVICE(p);
   TN_HIP(launch_polydot_gadget(p, a, bhat, bhat_sets == 1, c, batch, terms, base_log, (flags & TN_GADGET_BALANCED) != 0, pick_stream(p, stream)));
   return TN_OK;
 }
 
 extern "C" tn_status tn_pointwise_mul_dev(tn_plan* p, const void* a, const void* b, void* c, size_t batch, void* stream) {
-  if (!p) return fail(TN_EINVAL, "tn_pointwise_mul_dev: plan is NULL");
-  if (batch > 0xffffffffull) return fail(TN_EINVAL, "tn_pointwise_mul_dev: batch too large");
-  if (batch && (!a || !b || !c)) return fail(TN_EINVAL, "tn_pointwise_mul_dev: NULL buffer");
+  TN_CHECK("tn_pointwise_mul_dev", check_pointwise(k, a, b, c, batch));
   TN_ON_DEVICE(p);
   TN_HIP(launch_pointwise(p, a, b, c, batch, pick_stream(p, stream)));
   return TN_OK;
 }
 
 extern "C" tn_status tn_schoolbook_dev(tn_plan* p, const void* a, const void* b, void* c, size_t batch, void* stream) {
-  tn_status st = check_ptrs(p, a, b, c, batch, "tn_schoolbook_dev");
-  if (st) return st;
+  TN_CHECK("tn_schoolbook_dev", check_rows(k, a, b, c, batch));
   TN_ON_DEVICE(p);
   TN_HIP(launch_schoolbook(p, a, b, c, batch, pick_stream(p, stream)));
   return TN_OK;
@@ -417,22 +306,13 @@ extern "C" tn_status tn_plan_export_table(tn_plan* p, int which, void* host_out)
 
 static tn_status ntt_dev(tn_plan* p, int mode, const void* in, void* out, size_t batch, tn_variant variant, void* stream,
                          void* trace, const char* fn) {
-  tn_status st = check_ptrs(p, in, in, out, batch, fn);
-  if (st) return st;
-  if (p->omega_only && mode == CG_TWIST_FWD) return fail(TN_EUNSUPPORTED, std::string(fn) + ": an omega-only plan has no psi to twist with");
+  TN_CHECK(fn, check_transform(k, in, out, batch, mode == CG_TWIST_FWD));
   TN_ON_DEVICE(p);
-  if (variant == TN_VARIANT_AUTO) variant = (p->has_fused && !trace) ? TN_VARIANT_FUSED : TN_VARIANT_CG;
-  if (variant == TN_VARIANT_FUSED) {
-    // register-tiled kernel: same results, no per-stage trace (its internal stages are not the CG stages)
-    if (!p->has_fused) return fail(TN_EUNSUPPORTED, std::string(fn) + ": fused kernel not built for this n; use TN_VARIANT_CG");
-    if (trace) return fail(TN_EUNSUPPORTED, std::string(fn) + ": per-stage traces need a CG variant");
-    const int fmode = mode == CG_NTT_FWD ? FNTT_CYCLIC_FWD : (mode == CG_NTT_INV ? FNTT_CYCLIC_INV : FNTT_TWIST_FWD);
-    TN_HIP(launch_ntt_fused(p, fmode, in, out, batch, pick_stream(p, stream)));
-    return TN_OK;
-  }
-  CgSel sel;
-  if (!cg_sel(variant, &sel)) return fail(TN_EINVAL, std::string(fn) + ": unknown variant");
-  TN_HIP(launch_cg(p, mode, sel.group, sel.layout, in, nullptr, out, trace, batch, pick_stream(p, stream)));
+  const KernelPick sel = pick_kernel(k.v, variant, trace != nullptr);
+  if (!k.kernel(sel, trace != nullptr)) return refused(k);
+  const int fmode = mode == CG_NTT_FWD ? FNTT_CYCLIC_FWD : (mode == CG_NTT_INV ? FNTT_CYCLIC_INV : FNTT_TWIST_FWD);
+  if (sel.fused) TN_HIP(launch_ntt_fused(p, fmode, in, out, batch, pick_stream(p, stream)));
+  else TN_HIP(launch_cg(p, mode, sel.group, sel.layout, in, nullptr, out, trace, batch, pick_stream(p, stream)));
   return TN_OK;
 }
 
@@ -445,6 +325,7 @@ extern "C" tn_status tn_ntt_inverse_dev(tn_plan* p, const void* in, void* out, s
 extern "C" tn_status tn_twisted_ntt_forward_dev(tn_plan* p, const void* in, void* out, size_t batch, tn_variant v, void* stream) {
   return ntt_dev(p, CG_TWIST_FWD, in, out, batch, v, stream, nullptr, "tn_twisted_ntt_forward_dev");
 }
+
 
 // ---- host-buffer conveniences ------------------------------------------------
 static tn_status ensure_scratch(tn_plan* p, size_t bytes) {
@@ -547,7 +428,7 @@ extern "C" tn_status tn_plan_set_host_chunk_rows(tn_plan* p, size_t rows) {
 }
 
 extern "C" tn_status tn_poly_mult_host(tn_plan* p, const void* a, const void* b, void* c, size_t batch, tn_variant variant) {
-  tn_status st = check_ptrs(p, a, b, c, batch, "tn_poly_mult_host");
+  tn_status st = rows_checked(p, a, b, c, batch, "tn_poly_mult_host");
   if (st || batch == 0) return st;
   std::lock_guard<std::mutex> host_lock(p->host_mu);
   TN_ON_DEVICE(p);
@@ -558,7 +439,7 @@ extern "C" tn_status tn_poly_mult_host(tn_plan* p, const void* a, const void* b,
 }
 
 static tn_status ntt_host(tn_plan* p, int mode, const void* in, void* out, void* trace, size_t batch, tn_variant v, const char* fn) {
-  tn_status st = check_ptrs(p, in, in, out, batch, fn);
+  tn_status st = rows_checked(p, in, in, out, batch, fn);
   if (st || batch == 0) return st;
   std::lock_guard<std::mutex> host_lock(p->host_mu);
   TN_ON_DEVICE(p);
@@ -590,7 +471,7 @@ extern "C" tn_status tn_twisted_ntt_forward_host(tn_plan* p, const void* in, voi
   return ntt_host(p, CG_TWIST_FWD, in, out, nullptr, batch, v, "tn_twisted_ntt_forward_host");
 }
 extern "C" tn_status tn_schoolbook_host(tn_plan* p, const void* a, const void* b, void* c, size_t batch) {
-  tn_status st = check_ptrs(p, a, b, c, batch, "tn_schoolbook_host");
+  tn_status st = rows_checked(p, a, b, c, batch, "tn_schoolbook_host");
   if (st || batch == 0) return st;
   std::lock_guard<std::mutex> host_lock(p->host_mu);
   TN_ON_DEVICE(p);
@@ -605,16 +486,14 @@ extern "C" tn_status tn_ntt_forward_trace_host(tn_plan* p, const void* in, void*
 }
 
 extern "C" tn_status tn_fill_lcg_dev(tn_plan* p, void* dst, size_t batch, uint64_t seed0, uint64_t seed_stride, void* stream) {
-  if (!p || (batch && !dst)) return fail(TN_EINVAL, "tn_fill_lcg_dev: NULL argument");
-  if (batch > 0xffffffffull) return fail(TN_EINVAL, "tn_fill_lcg_dev: batch too large");
+  TN_CHECK("tn_fill_lcg_dev", check_fill(k, dst != nullptr, batch));
   TN_ON_DEVICE(p);
   TN_HIP(launch_fill_lcg(p, dst, batch, seed0, seed_stride, pick_stream(p, stream)));
   return TN_OK;
 }
 
 extern "C" tn_status tn_checksum_rows_dev(tn_plan* p, const void* src, uint64_t* out, size_t batch, void* stream) {
-  if (!p || (batch && (!src || !out))) return fail(TN_EINVAL, "tn_checksum_rows_dev: NULL argument");
-  if (batch > 0xffffffffull) return fail(TN_EINVAL, "tn_checksum_rows_dev: batch too large");
+  TN_CHECK("tn_checksum_rows_dev", check_fill(k, src && out, batch));
   TN_ON_DEVICE(p);
   TN_HIP(launch_checksum(p, src, out, batch, pick_stream(p, stream)));
   return TN_OK;
@@ -630,7 +509,7 @@ extern "C" tn_status tn_plan_synchronize(tn_plan* p) {
 extern "C" tn_status tn_time_poly_mult_dev(tn_plan* p, const void* a, const void* b, void* c, size_t batch, tn_variant variant,
                                            int iters, float* ms_per_launch) {
   if (!ms_per_launch || iters < 1) return fail(TN_EINVAL, "tn_time_poly_mult_dev: bad iters/ms pointer");
-  tn_status st = check_ptrs(p, a, b, c, batch, "tn_time_poly_mult_dev");
+  tn_status st = rows_checked(p, a, b, c, batch, "tn_time_poly_mult_dev");
   if (st) return st;
   std::lock_guard<std::mutex> host_lock(p->host_mu);
   TN_ON_DEVICE(p);
@@ -647,9 +526,7 @@ extern "C" tn_status tn_time_poly_mult_dev(tn_plan* p, const void* a, const void
 
 extern "C" const char* tn_kernel_name(const tn_plan* p, tn_variant variant) {
   if (!p) return "";
-  if (variant == TN_VARIANT_AUTO) variant = p->has_fused ? TN_VARIANT_FUSED : TN_VARIANT_CG;
-  if (variant == TN_VARIANT_FUSED) return fused_kernel_name(p);
-  CgSel sel;
-  if (cg_sel(variant, &sel)) return cg_kernel_name(p, sel.group, sel.layout);
-  return "";
+  const KernelPick sel = pick_kernel(view(p), variant);
+  if (sel.fused) return fused_kernel_name(p);
+  return sel.known ? cg_kernel_name(p, sel.group, sel.layout) : "";
 }

@@ -139,10 +139,11 @@ def build_id() -> str:
     return load_library().tn_build_id().decode()
 
 
-def _check(lib, status: int):
+def _check(lib, status: int, last_error=None):
+    """Raise for a status other than TN_OK; last_error: the getter of the text (tn_multi_* keep their own)."""
     if status == TN_OK:
         return
-    msg = lib.tn_last_error().decode() or lib.tn_status_string(status).decode()
+    msg = (last_error or lib.tn_last_error)().decode() or lib.tn_status_string(status).decode()
     if status == TN_EBADLEN:
         raise ValueError(msg)          # the reference raises ValueError on a wrong length (cg_ntt.py:36-37,:79-80)
     raise TinyNttError(status, msg)
@@ -310,19 +311,52 @@ class Plan:
     def _binary_dev(self, fn, a, b, out, stream, *extra):
         """Shared marshalling of the device-only binary operators; numpy inputs are staged through torch."""
         import torch
-        host = not _is_torch(a)
-        squeeze = host and np.ndim(a) == 1
+        a, rows, host, one = self._rows_in(a)
         if host:
-            a, b = self.to_device(a), self.to_device(b)
-        rows = self._dev_rows(a, "a")
+            b = self.to_device(b)
         if self._dev_rows(b, "b") != rows:
             raise ValueError(f"Expected {self.n} coefficients")
         c = out if out is not None else torch.empty_like(a)
         _check(self._lib, fn(self._h, a.data_ptr(), b.data_ptr(), c.data_ptr(), rows, *extra, self._stream_ptr(stream)))
+        return self._result(c, host, host and one)
+
+    # ---- the prepared family: one marshalling path --------------------------------
+    def _rows_in(self, a):
+        """a as a contiguous device tensor of rows -> (tensor, rows, came from the host, one polynomial)."""
+        host = not _is_torch(a)
+        one = (np.ndim(a) if host else a.dim()) == 1
+        if host:
+            a = self.to_device(a)
+        return a, self._dev_rows(a, "a"), host, one
+
+    def _own_prepared(self, prepared, fn, which):
+        if not isinstance(prepared, PreparedOperand):
+            raise TypeError(f"{fn}: the {which} must come from Plan.prepare (or Plan.poly_dot_hat with keep_prepared)")
+        if prepared.plan is not self:
+            raise TinyNttError(TN_EINVAL, f"{fn}: the prepared operand belongs to another plan")
+
+    @staticmethod
+    def _sets(prepared, batch, terms, which="prepared operand"):
+        """bhat_sets of the C ABI: 1 when `prepared` holds one set of `terms` rows for every output row, batch when a set per row."""
+        if prepared.rows not in (terms, batch * terms):
+            raise ValueError(f"Expected a {which} of {terms} or {batch * terms} rows, got {prepared.rows}")
+        return 1 if prepared.rows == terms else batch
+
+    def _out_rows(self, out, batch, device):
+        """out, or a new tensor on `device`: `batch` rows of the plan's words."""
+        import torch
+        c = out if out is not None else torch.empty((batch, self.n), dtype=self.torch_dtype, device=device)
+        if self._dev_rows(c, "out") != batch:
+            raise ValueError(f"Expected an output of {batch} rows of {self.n} coefficients")
+        return c
+
+    def _result(self, c, host, one, out=None):
+        """Hand c back: a host array where the input came from the host; row 0 alone where one polynomial went in (and, on the
+        device, the caller gave no `out`)."""
         if host:
             res = self.to_host(c)
-            return res[0] if squeeze else res
-        return c
+            return res[0] if one else res
+        return c[0] if one and out is None else c
 
     def prepare(self, b, out=None, stream=None) -> PreparedOperand:
         """Transform b once (tn_prepare_dev): b is one polynomial or [rows, n], host values (taken mod q) or a device tensor."""
@@ -340,33 +374,19 @@ class Plan:
         """c[r] = a[r] * b[r] in Z_q[x]/(x^n+1) with b given as Plan.prepare(b) (tn_poly_mult_prepared_dev): two transforms per
         row instead of three.  A prepared operand of ONE row is multiplied into every row of a."""
         import torch
-        if not isinstance(prepared, PreparedOperand):
-            raise TypeError("poly_mult_prepared: the second operand must come from Plan.prepare")
-        if prepared.plan is not self:
-            raise TinyNttError(TN_EINVAL, "poly_mult_prepared: the prepared operand belongs to another plan")
-        host = not _is_torch(a)
-        squeeze = host and np.ndim(a) == 1
-        if host:
-            a = self.to_device(a)
-        rows = self._dev_rows(a, "a")
+        self._own_prepared(prepared, "poly_mult_prepared", "second operand")
+        a, rows, host, one = self._rows_in(a)
         c = out if out is not None else torch.empty_like(a)
         self._dev_rows(c, "out")
         _check(self._lib, self._lib.tn_poly_mult_prepared_dev(self._h, a.data_ptr(), prepared.tensor.data_ptr(), prepared.rows, c.data_ptr(), rows,
                                                               self._stream_ptr(stream)))
-        if host:
-            res = self.to_host(c)
-            return res[0] if squeeze else res
-        return c
+        return self._result(c, host, host and one)
 
     def poly_dot_prepared(self, a, prepared: PreparedOperand, out=None, stream=None):
         """c[r] = sum_j a[r][j] * b[r][j] in Z_q[x]/(x^n+1) with b given as Plan.prepare(b) (tn_poly_dot_prepared_dev): one inverse
         transform per output row.  a is (batch, terms, n), or (terms, n) for one output polynomial; the prepared operand has
         batch * terms rows, or `terms` rows that every output row is multiplied by.  Returns (batch, n) or (n,)."""
-        import torch
-        if not isinstance(prepared, PreparedOperand):
-            raise TypeError("poly_dot_prepared: the second operand must come from Plan.prepare")
-        if prepared.plan is not self:
-            raise TinyNttError(TN_EINVAL, "poly_dot_prepared: the prepared operand belongs to another plan")
+        self._own_prepared(prepared, "poly_dot_prepared", "second operand")
         host = not _is_torch(a)
         if host:
             a = np.asarray(a)
@@ -381,36 +401,18 @@ class Plan:
             if not a.is_contiguous():
                 raise TinyNttError(TN_EINVAL, f"a: need a contiguous tensor of {self.elem_bytes}-byte integers")
             self._dev_rows(a.reshape(batch * terms, self.n), "a")
-        if prepared.rows not in (terms, batch * terms):
-            raise ValueError(f"Expected a prepared operand of {terms} or {batch * terms} rows, got {prepared.rows}")
-        sets = 1 if prepared.rows == terms else batch
-        c = out if out is not None else torch.empty((batch, self.n), dtype=self.torch_dtype, device=a.device)
-        if self._dev_rows(c, "out") != batch:
-            raise ValueError(f"Expected an output of {batch} rows of {self.n} coefficients")
+        sets = self._sets(prepared, batch, terms)
+        c = self._out_rows(out, batch, a.device)
         _check(self._lib, self._lib.tn_poly_dot_prepared_dev(self._h, a.data_ptr(), prepared.tensor.data_ptr(), sets, c.data_ptr(), batch, terms,
                                                              self._stream_ptr(stream)))
-        if host:
-            res = self.to_host(c)
-            return res[0] if squeeze else res
-        if out is None and squeeze:
-            return c[0]
-        return c
-
-    def _own_prepared(self, prepared, fn, which):
-        if not isinstance(prepared, PreparedOperand):
-            raise TypeError(f"{fn}: the {which} must come from Plan.prepare (or Plan.poly_dot_hat with keep_prepared)")
-        if prepared.plan is not self:
-            raise TinyNttError(TN_EINVAL, f"{fn}: the prepared operand belongs to another plan")
+        return self._result(c, host, squeeze, out)
 
     def unprepare(self, prepared: PreparedOperand, out=None, stream=None):
         """The polynomials whose prepared form `prepared` holds (tn_unprepare_dev): a device tensor (rows, n) of canonical residues,
         the inverse of Plan.prepare."""
-        import torch
         self._own_prepared(prepared, "unprepare", "operand")
         rows = prepared.rows
-        x = out if out is not None else torch.empty((rows, self.n), dtype=self.torch_dtype, device=prepared.tensor.device)
-        if self._dev_rows(x, "out") != rows:
-            raise ValueError(f"Expected an output of {rows} rows of {self.n} coefficients")
+        x = self._out_rows(out, rows, prepared.tensor.device)
         _check(self._lib, self._lib.tn_unprepare_dev(self._h, prepared.tensor.data_ptr(), x.data_ptr(), rows, self._stream_ptr(stream)))
         return x
 
@@ -419,32 +421,19 @@ class Plan:
         batch * terms rows (the terms of one output row are consecutive); b_prepared holds as many, or `terms` rows that every
         output row is multiplied by.  Returns a device tensor (batch, n) of coefficients, or, with keep_prepared, a
         PreparedOperand of batch rows (no transform runs; prepared rows of one plan add word-wise mod q)."""
-        import torch
         self._own_prepared(a_prepared, "poly_dot_hat", "first operand")
         self._own_prepared(b_prepared, "poly_dot_hat", "second operand")
         terms = int(terms)
         if terms < 1 or a_prepared.rows % terms:
             raise ValueError(f"Expected a first operand of batch * {terms} rows, got {a_prepared.rows}")
         batch = a_prepared.rows // terms
-        if b_prepared.rows not in (terms, batch * terms):
-            raise ValueError(f"Expected a second operand of {terms} or {batch * terms} rows, got {b_prepared.rows}")
-        sets = 1 if b_prepared.rows == terms else batch
+        sets = self._sets(b_prepared, batch, terms, "second operand")
         if isinstance(out, PreparedOperand):
             out = out.tensor
-        c = out if out is not None else torch.empty((batch, self.n), dtype=self.torch_dtype, device=a_prepared.tensor.device)
-        if self._dev_rows(c, "out") != batch:
-            raise ValueError(f"Expected an output of {batch} rows of {self.n} coefficients")
+        c = self._out_rows(out, batch, a_prepared.tensor.device)
         _check(self._lib, self._lib.tn_poly_dot_hat_dev(self._h, a_prepared.tensor.data_ptr(), b_prepared.tensor.data_ptr(), sets, c.data_ptr(), batch,
                                                         terms, 1 if keep_prepared else 0, self._stream_ptr(stream)))
         return PreparedOperand(self, c, batch) if keep_prepared else c
-
-    def _gadget_rows(self, a):
-        """a as a contiguous device tensor (batch, n) -> (tensor, batch, came from the host, one polynomial)."""
-        host = not _is_torch(a)
-        squeeze = (np.ndim(a) if host else a.dim()) == 1
-        if host:
-            a = self.to_device(a)
-        return a, self._dev_rows(a, "a"), host, squeeze
 
     def gadget_decompose(self, a, terms, base_log, balanced=False, out=None, stream=None):
         """The base-2^base_log digits of every coefficient of a, taken mod q (tn_gadget_decompose_dev; include/tinyntt.h has the
@@ -452,7 +441,7 @@ class Plan:
         residues, digit polynomial j of row r at [r, j].  balanced: digits in [-B/2, B/2), negative ones stored as q + d.  Works
         on every plan."""
         import torch
-        a, batch, host, squeeze = self._gadget_rows(a)
+        a, batch, host, one = self._rows_in(a)
         terms = int(terms)
         if terms < 1:
             raise ValueError(f"Expected terms >= 1, got {terms}")
@@ -461,39 +450,23 @@ class Plan:
             raise ValueError(f"Expected an output of {batch} x {terms} rows of {self.n} coefficients")
         _check(self._lib, self._lib.tn_gadget_decompose_dev(self._h, a.data_ptr(), d.data_ptr(), batch, terms, int(base_log),
                                                             GADGET_BALANCED if balanced else 0, self._stream_ptr(stream)))
-        if host:
-            res = self.to_host(d.reshape(batch * terms, self.n)).reshape(batch, terms, self.n)
-            return res[0] if squeeze else res
-        if out is None:
-            d = d.reshape(batch, terms, self.n)
-            return d[0] if squeeze else d
-        return d
+        return self._result(d.reshape(batch, terms, self.n) if host else d, host, one, out)
 
     def poly_gadget_dot_prepared(self, a, prepared: PreparedOperand, terms, base_log, balanced=False, out=None, stream=None):
         """c[r] = sum_j digit_j(a[r]) * b[r][j] in Z_q[x]/(x^n+1) with b given as Plan.prepare(b) (tn_poly_gadget_dot_prepared_dev):
         the digits of gadget_decompose are cut inside the kernel, so a is read once and they never reach memory.  a is (batch, n)
         or (n,); the prepared operand has batch * terms rows, or `terms` rows that every output row is multiplied by.  Returns
         (batch, n) or (n,), bit-identical to poly_dot_prepared(gadget_decompose(a, ...), prepared)."""
-        import torch
         self._own_prepared(prepared, "poly_gadget_dot_prepared", "second operand")
-        a, batch, host, squeeze = self._gadget_rows(a)
+        a, batch, host, one = self._rows_in(a)
         terms = int(terms)
         if terms < 1:
             raise ValueError(f"Expected terms >= 1, got {terms}")
-        if prepared.rows not in (terms, batch * terms):
-            raise ValueError(f"Expected a prepared operand of {terms} or {batch * terms} rows, got {prepared.rows}")
-        sets = 1 if prepared.rows == terms else batch
-        c = out if out is not None else torch.empty((batch, self.n), dtype=self.torch_dtype, device=a.device)
-        if self._dev_rows(c, "out") != batch:
-            raise ValueError(f"Expected an output of {batch} rows of {self.n} coefficients")
+        sets = self._sets(prepared, batch, terms)
+        c = self._out_rows(out, batch, a.device)
         _check(self._lib, self._lib.tn_poly_gadget_dot_prepared_dev(self._h, a.data_ptr(), prepared.tensor.data_ptr(), sets, c.data_ptr(), batch, terms,
                                                                     int(base_log), GADGET_BALANCED if balanced else 0, self._stream_ptr(stream)))
-        if host:
-            res = self.to_host(c)
-            return res[0] if squeeze else res
-        if out is None and squeeze:
-            return c[0]
-        return c
+        return self._result(c, host, one, out)
 
     def cyclic_poly_mult(self, a, b, variant="auto", out=None, stream=None):
         """Untwisted product forward->pointwise->inverse: python_poly_mult (test_ntt_poly_mult.py:38-43)."""
@@ -613,11 +586,7 @@ class MultiPlan:
         self._h = ctypes.c_void_p()
         arr = (ctypes.c_int * len(devices))(*devices) if devices is not None else None
         st = self._lib.tn_multi_create(ctypes.byref(self._h), int(n), int(q), int(psi) % int(q), arr, len(devices) if devices is not None else 0, int(flags))
-        if st != TN_OK:
-            msg = self._lib.tn_multi_last_error().decode()
-            if st == TN_EBADLEN:
-                raise ValueError(msg)
-            raise TinyNttError(st, msg)
+        _check(self._lib, st, self._lib.tn_multi_last_error)
         self.n, self.q, self.psi = int(n), int(q), int(psi) % int(q)
         self.size = int(self._lib.tn_multi_size(self._h))
         self.devices = [int(self._lib.tn_multi_device(self._h, i)) for i in range(self.size)]
@@ -648,38 +617,35 @@ class MultiPlan:
             raise ValueError(f"Expected {self.n} coefficients")
         hc = np.empty_like(ha)
         st = self._lib.tn_multi_poly_mult_host(self._h, ha.ctypes.data, hb.ctypes.data, hc.ctypes.data, ha.shape[0], _variant(variant))
-        if st != TN_OK:
-            raise TinyNttError(st, self._lib.tn_multi_last_error().decode())
+        _check(self._lib, st, self._lib.tn_multi_last_error)
         return hc
 
 
 _plan_cache = {}
 
 
-def get_plan(n: int, q: int, psi: int, device: int = 0, flags: int = 0) -> Plan:
-    key = (int(n), int(q), int(psi) % int(q), int(device), int(flags))
+def _cached_plan(key, make) -> Plan:
     p = _plan_cache.get(key)
     if p is None:
-        p = _plan_cache[key] = Plan(*key)
+        p = _plan_cache[key] = make()
     return p
+
+
+def get_plan(n: int, q: int, psi: int, device: int = 0, flags: int = 0) -> Plan:
+    key = (int(n), int(q), int(psi) % int(q), int(device), int(flags))
+    return _cached_plan(key, lambda: Plan(*key))
 
 
 def get_omega_plan(n: int, q: int, omega: int, device: int = 0) -> Plan:
     """Cached omega-only plan: the transforms cg_ntt(a, omega_n, modulus) / cg_intt for any omega_n (cg_ntt.py:29-75)."""
     key = ("omega", int(n), int(q), int(omega) % int(q), int(device))
-    p = _plan_cache.get(key)
-    if p is None:
-        p = _plan_cache[key] = Plan(int(n), int(q), 0, int(device), 0, omega=int(omega))
-    return p
+    return _cached_plan(key, lambda: Plan(int(n), int(q), 0, int(device), 0, omega=int(omega)))
 
 
 def get_general_plan(n: int, q: int, psi: int, device: int = 0) -> Plan:
     """Cached general plan (tn_plan_create_general): nwc_poly_mult for any psi_2n / modulus, as cg_ntt.py:78-92 computes it."""
     key = ("general", int(n), int(q), int(psi) % int(q), int(device))
-    p = _plan_cache.get(key)
-    if p is None:
-        p = _plan_cache[key] = Plan(int(n), int(q), int(psi), int(device), 0, general=True)
-    return p
+    return _cached_plan(key, lambda: Plan(int(n), int(q), int(psi), int(device), 0, general=True))
 
 
 def get_poly_plan(n: int, q: int, psi: int, device: int = 0) -> Plan:
