@@ -279,6 +279,37 @@ tn_status tn_poly_gadget_dot_prepared_dev(tn_plan *plan, const void *a, const vo
                                           size_t terms, uint32_t base_log, uint32_t flags, void *stream);
 
 /*
+ * GADGET product with several output components: both components of a key switch from ONE launch.  A key-switch key is `terms`
+ * pairs (b_j, a_j) and the result is (sum_j d_j b_j, sum_j d_j a_j) for the same digits d_j of the same polynomial: a is read,
+ * cut into digits and transformed ONCE per term for all components, instead of once per component.
+ *
+ * tn_poly_gadget_multidot_prepared_dev: c[r][o] = sum_{j < terms} digit_j(a[r]) * b[s][o][j] in Z_q[x]/(x^n+1),
+ * s = (bhat_sets == 1 ? 0 : r), r < batch, o < outs.  a is [batch][n], any word values; bhat is [bhat_sets][outs][terms][n] as
+ * tn_prepare_dev wrote it for bhat_sets * outs * terms rows (for a shared set, bhat + o * terms * n is a valid shared set of
+ * tn_poly_gadget_dot_prepared_dev); c is [batch][outs][n], canonical residues.  Digits, flags and base_log are exactly those of
+ * tn_poly_gadget_dot_prepared_dev, and the result is BIT-IDENTICAL to `outs` calls of it, one per component.
+ * outs == 1 is that call and runs its kernel; outs == 2 runs a kernel of its own (`terms` forward transforms and two inverses
+ * per output row instead of 2 * terms and two).  outs > 2 is NOT SUPPORTED: TN_EUNSUPPORTED.
+ *
+ * When to use which (MI355X, profiles/gadget_pair_ab.txt; slowest repeat of the one launch against the fastest repeat of two
+ * tn_poly_gadget_dot_prepared_dev launches on the same buffers, balanced digits, terms 2 - 4):
+ *   - both components wanted: one tn_poly_gadget_multidot_prepared_dev launch is faster at every measured point, x 0.70 - 0.76 of
+ *     the two launches at n = 4096 / 60-bit, 65,536 rows and x 0.74 - 0.79 at n = 1024 / 24-bit, 4,096 rows, shared set or a set
+ *     per row.  No measured point is slower.  The gain grows with terms.
+ *   - one component wanted: outs = 1 is tn_poly_gadget_dot_prepared_dev, at its cost.
+ *   - n = 256, n = 8192 and the canonical policy were not measured.
+ *
+ * TN_EINVAL: everything tn_poly_gadget_dot_prepared_dev refuses, in its order, with the row limit on batch * outs * terms
+ * (<= 2^31 - 1) and the overlap check on c's batch * outs rows against a's batch rows and bhat's bhat_sets * outs * terms rows
+ * (byte ranges); outs == 0.  TN_EUNSUPPORTED: a plan without the fused kernels; outs > 2 (looked at after the plan, before
+ * terms, flags and base_log).  batch == 0 succeeds and launches nothing.  The call enqueues on the stream and returns, and may
+ * be stream-captured (a captured launch hands rows out at the fixed stride).  No cyclic variant, no *_host form and no
+ * tn_multi_* form.
+ */
+tn_status tn_poly_gadget_multidot_prepared_dev(tn_plan *plan, const void *a, const void *bhat, size_t bhat_sets, void *c, size_t batch,
+                                               size_t outs, size_t terms, uint32_t base_log, uint32_t flags, void *stream);
+
+/*
  * The *_host entry points cut the batch into chunks that flow H2D -> kernel -> D2H on three
  * streams through a fixed set of device staging slots (copies overlap the kernels when the host
  * buffers are pinned; device staging stays bounded whatever the batch).  rows = rows per chunk,

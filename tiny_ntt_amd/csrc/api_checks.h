@@ -51,12 +51,17 @@ struct __attribute__((visibility("hidden"))) ApiCheck {          // (hidden, sta
   }
   bool out_prepared(int flag) { return flag == 0 || flag == 1 || fail(TN_EINVAL, "out_prepared must be 0 (coefficients) or 1 (prepared rows)"); }
   // what both gadget calls ask: terms >= 1, known flags, 0 < base_log, 2^base_log < q, no shift reaches the word width
-  bool gadget(size_t batch, size_t terms_, uint32_t base_log, uint32_t flags) {
+  bool gadget(size_t batch, size_t terms_, uint32_t base_log, uint32_t flags, const char* count = "batch * terms") {
     if (!terms(terms_)) return false;
     if (flags & ~(uint32_t)TN_GADGET_BALANCED) return fail(TN_EINVAL, "unknown flag bit");
     if (base_log == 0 || base_log >= 64 || (((uint64_t)1) << base_log) >= v.q) return fail(TN_EINVAL, "need 1 <= base_log and 2^base_log < q");
     if (terms_ - 1 > 63 / base_log) return fail(TN_EINVAL, "(terms - 1) * base_log must be below 64");
-    return rows(batch, terms_, "batch * terms", "digit rows");
+    return rows(batch, terms_, count, "digit rows");
+  }
+  // output components of tn_poly_gadget_multidot_prepared_dev: one runs the gadget kernel, two the kernel built for them
+  bool outs(size_t outs_) {
+    if (!outs_) return fail(TN_EINVAL, "outs must be at least 1");
+    return outs_ <= 2 || fail(TN_EUNSUPPORTED, "more than 2 output components are not supported");
   }
   // The byte ranges of out_rows rows at out and in_rows rows at in share no byte: the kernels prefetch the next row's input
   // while a row's result is being stored.  Compared as integers: a caller may pass any address, also one near 0.
@@ -110,6 +115,17 @@ static inline bool check_gadget_dot(ApiCheck& k, const void* a, const void* bhat
   return k.plan() && k.fused() && k.gadget(batch, terms, base_log, flags) && k.work(batch) && k.buffers(a && bhat && c) &&
          k.sets(sets, batch, "bhat_sets", "one set of operands for every row") && k.apart(c, batch, a, batch, "an input") &&
          k.apart(c, batch, bhat, sets * terms, "an input");
+}
+// batch * outs for a row limit; a batch that is above the limit by itself stands as it is (times outs it could wrap size_t)
+static inline size_t rows_times(size_t batch, size_t outs) { return batch > 0x7fffffffull ? batch : batch * outs; }
+// check_gadget_dot's list with the component count behind the plan's: the row limit holds for batch * outs * terms, c has
+// batch * outs rows and bhat sets * outs * terms
+static inline bool check_gadget_multidot(ApiCheck& k, const void* a, const void* bhat, size_t sets, const void* c, size_t batch, size_t outs,
+                                         size_t terms, uint32_t base_log, uint32_t flags) {
+  return k.plan() && k.fused() && k.outs(outs) &&
+         k.gadget(rows_times(batch, outs), terms, base_log, flags, "batch * outs * terms") && k.work(batch) &&
+         k.buffers(a && bhat && c) && k.sets(sets, batch, "bhat_sets", "one set of operands for every row") &&
+         k.apart(c, batch * outs, a, batch, "an input") && k.apart(c, batch * outs, bhat, sets * outs * terms, "an input");
 }
 static inline bool check_pointwise(ApiCheck& k, const void* a, const void* b, const void* c, size_t batch) {      // in place is allowed
   return k.plan() && k.rows_wide(batch) && k.buffers(!batch || (a && b && c));

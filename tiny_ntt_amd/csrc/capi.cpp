@@ -269,6 +269,17 @@ extern "C" tn_status tn_poly_gadget_dot_prepared_dev(tn_plan* p, const void* a, 
   return TN_OK;
 }
 
+// one component is the gadget kernel; two come from one forward transform per term (polydot_gadget2_kernel)
+extern "C" tn_status tn_poly_gadget_multidot_prepared_dev(tn_plan* p, const void* a, const void* bhat, size_t bhat_sets, void* c, size_t batch,
+                                                          size_t outs, size_t terms, uint32_t base_log, uint32_t flags, void* stream) {
+  TN_CHECK("tn_poly_gadget_multidot_prepared_dev", check_gadget_multidot(k, a, bhat, bhat_sets, c, batch, outs, terms, base_log, flags));
+  TN_ON_DEVICE(p);
+  const bool balanced = (flags & TN_GADGET_BALANCED) != 0;
+  if (outs == 1) TN_HIP(launch_polydot_gadget(p, a, bhat, bhat_sets == 1, c, batch, terms, base_log, balanced, pick_stream(p, stream)));
+  else TN_HIP(launch_polydot_gadget2(p, a, bhat, bhat_sets == 1, c, batch, terms, base_log, balanced, pick_stream(p, stream)));
+  return TN_OK;
+}
+
 extern "C" tn_status tn_pointwise_mul_dev(tn_plan* p, const void* a, const void* b, void* c, size_t batch, void* stream) {
   TN_CHECK("tn_pointwise_mul_dev", check_pointwise(k, a, b, c, batch));
   TN_ON_DEVICE(p);

@@ -669,6 +669,46 @@ TN_HD void dot_accumulate(E (&acc)[Cfg::R], const E (&x)[Cfg::R], const Arith<E>
   for (int r = 0; r < Cfg::R; ++r) acc[r] = dot_accumulate_one<E, Pol>(acc[r], x[r], ar);
 }
 
+// acc += xa * xb, register pair by register pair, with xa LEFT AS IT IS (polydot_gadget2_kernel: one transformed digit row is
+// multiplied by several prepared rows).  pointwise() and basecase() overwrite their first operand; here the product of a pair
+// goes into temporaries and straight into the sum (the pointwise products one at a time), so no further row of live words
+// appears.  Both see the operands those two see (the base case's fold of xa is taken on the copy), and the sum is
+// dot_accumulate_one's.  zeta: the base case's records as basecase() takes them (unused otherwise).
+// after_pair(integral_constant i) runs once pair i is in the sum, when registers 2i and 2i + 1 of xb are dead (basecase_each).
+template <typename E, typename Cfg, typename Pol, bool BC, typename F>
+TN_HD void dot_product_into(E (&acc)[Cfg::R], const E (&xa)[Cfg::R], const E (&xb)[Cfg::R], const typename TwOf<E>::type* zeta,
+                            const Arith<E>& ar, F&& after_pair) {
+  (void)zeta;
+  static_for<0, Cfg::R / 2>([&](auto i_) {
+    constexpr int r = 2 * decltype(i_)::value;
+    E p0 = xa[r], p1 = xa[r + 1];
+    if constexpr (BC) {
+      typedef SchedOf<Pol, Cfg, true> SO;
+      static_assert(Pol::split && Cfg::pos(Cfg::PHASES - 1) == 0, "base case: split policy, pairs in neighbouring registers");
+      if constexpr (SO::bc_fold(r)) p0 = fold(p0, ar.k, ar.fold_c);
+      if constexpr (SO::bc_fold(r + 1)) p1 = fold(p1, ar.k, ar.fold_c);
+      basecase_pair(p0, p1, xb[r], xb[r + 1], zeta[r / 2], ar);
+    } else {
+      typedef SchedOf<Pol, Cfg> SO;
+      static_assert(SO::pw_ok(), "pointwise_lazy: unfolded operand bound");
+      if (Pol::lazy) p0 = pointwise_lazy(p0, SO::pw_fold_b() ? fold(xb[r], ar.k, ar.fold_c) : xb[r], ar);
+      else p0 = mulmod_barrett(p0, xb[r], ar.q, ar.mu, ar.k);
+      acc[r] = dot_accumulate_one<E, Pol>(acc[r], p0, ar);
+      sched_fence();                   // one product in flight at a time: the digit row stays live beside it
+      if (Pol::lazy) p1 = pointwise_lazy(p1, SO::pw_fold_b() ? fold(xb[r + 1], ar.k, ar.fold_c) : xb[r + 1], ar);
+      else p1 = mulmod_barrett(p1, xb[r + 1], ar.q, ar.mu, ar.k);
+      acc[r + 1] = dot_accumulate_one<E, Pol>(acc[r + 1], p1, ar);
+    }
+    sched_fence();                     // one pair in flight at a time: bounds the live temporaries
+    if constexpr (BC) {
+      acc[r] = dot_accumulate_one<E, Pol>(acc[r], p0, ar);
+      acc[r + 1] = dot_accumulate_one<E, Pol>(acc[r + 1], p1, ar);
+      sched_fence();
+    }
+    after_pair(i_);
+  });
+}
+
 // Gadget decomposition (tn_gadget_decompose_dev, polydot_gadget_kernel: kernels_gadget.hip).
 // gadget_canon: ANY word of the lane -> its residue in [0, q), exactly.
 //   lazy: one fold() of any word lands below 2q (h_lazy_ok, plan_tables.h: c (floor(2^W / 2^k) + 1) <= q; replayed for the

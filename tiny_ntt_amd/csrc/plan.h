@@ -196,6 +196,10 @@ hipError_t launch_gadget_decompose(const tn_plan* p, const void* a, void* digits
                                    hipStream_t s);
 hipError_t launch_polydot_gadget(const tn_plan* p, const void* a, const void* bhat, bool shared, void* c, size_t batch, size_t terms,
                                  tn::u32 base_log, bool balanced, hipStream_t s);
+// ... with two output components from one forward transform per term (tn_poly_gadget_multidot_prepared_dev, outs == 2):
+// c[r][o] = sum_j digit_j(a[r]) * b[shared ? 0 : r][o][j], o < 2
+hipError_t launch_polydot_gadget2(const tn_plan* p, const void* a, const void* bhat, bool shared, void* c, size_t batch, size_t terms,
+                                  tn::u32 base_log, bool balanced, hipStream_t s);
 hipError_t launch_cg(const tn_plan* p, int mode, int group, int layout, const void* a, const void* b, void* out,
                      void* trace, size_t batch, hipStream_t s);
 hipError_t launch_pointwise(const tn_plan* p, const void* a, const void* b, void* c, size_t batch, hipStream_t s);

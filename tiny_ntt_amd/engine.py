@@ -40,7 +40,7 @@ EXPORTED_SYMBOLS = (
     "tn_plan_elem_bytes", "tn_plan_device", "tn_plan_has_fused", "tn_plan_is_lazy",
     "tn_poly_mult_dev", "tn_poly_mult_host", "tn_plan_set_host_chunk_rows", "tn_cyclic_poly_mult_dev", "tn_pointwise_mul_dev", "tn_schoolbook_dev",
     "tn_prepare_dev", "tn_poly_mult_prepared_dev", "tn_poly_dot_prepared_dev", "tn_unprepare_dev", "tn_poly_dot_hat_dev",
-    "tn_gadget_decompose_dev", "tn_poly_gadget_dot_prepared_dev",
+    "tn_gadget_decompose_dev", "tn_poly_gadget_dot_prepared_dev", "tn_poly_gadget_multidot_prepared_dev",
     "tn_plan_export_table", "tn_ntt_forward_dev", "tn_ntt_inverse_dev",
     "tn_ntt_forward_host", "tn_ntt_inverse_host", "tn_ntt_forward_trace_host", "tn_twisted_ntt_forward_dev",
     "tn_twisted_ntt_forward_host", "tn_schoolbook_host",
@@ -100,6 +100,7 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.tn_poly_dot_hat_dev.argtypes = [vp, vp, vp, sz, vp, sz, sz, ci, vp]
     lib.tn_gadget_decompose_dev.argtypes = [vp, vp, vp, sz, sz, u32, u32, vp]
     lib.tn_poly_gadget_dot_prepared_dev.argtypes = [vp, vp, vp, sz, vp, sz, sz, u32, u32, vp]
+    lib.tn_poly_gadget_multidot_prepared_dev.argtypes = [vp, vp, vp, sz, vp, sz, sz, sz, u32, u32, vp]
     lib.tn_schoolbook_dev.argtypes = [vp, vp, vp, vp, sz, vp]
     lib.tn_plan_export_table.argtypes = [vp, ci, vp]
     for name in ("tn_ntt_forward_dev", "tn_ntt_inverse_dev", "tn_twisted_ntt_forward_dev"):
@@ -467,6 +468,27 @@ class Plan:
         _check(self._lib, self._lib.tn_poly_gadget_dot_prepared_dev(self._h, a.data_ptr(), prepared.tensor.data_ptr(), sets, c.data_ptr(), batch, terms,
                                                                     int(base_log), GADGET_BALANCED if balanced else 0, self._stream_ptr(stream)))
         return self._result(c, host, one, out)
+
+    def poly_gadget_multidot_prepared(self, a, prepared: PreparedOperand, outs, terms, base_log, balanced=False, out=None, stream=None):
+        """c[r][o] = sum_j digit_j(a[r]) * b[r][o][j] for o < outs (tn_poly_gadget_multidot_prepared_dev): the `outs` components of a
+        key switch from ONE launch, the digits cut and transformed once for all of them.  a is (batch, n) or (n,); the prepared
+        operand has batch * outs * terms rows ([batch][outs][terms]), or outs * terms rows that every output row is multiplied
+        by.  outs is 1 or 2.  Returns (batch, outs, n) or (outs, n), bit-identical to poly_gadget_dot_prepared per component."""
+        import torch
+        self._own_prepared(prepared, "poly_gadget_multidot_prepared", "second operand")
+        a, batch, host, one = self._rows_in(a)
+        outs, terms = int(outs), int(terms)
+        if terms < 1 or outs < 1:
+            raise ValueError(f"Expected terms >= 1 and outs >= 1, got {terms} and {outs}")
+        sets = self._sets(prepared, batch, outs * terms)
+        c = out if out is not None else torch.empty((batch, outs, self.n), dtype=self.torch_dtype, device=a.device)
+        if not _is_torch(c) or c.numel() != batch * outs * self.n or not c.is_contiguous():
+            raise ValueError(f"Expected an output of {batch} x {outs} rows of {self.n} coefficients")
+        self._dev_rows(c.reshape(batch * outs, self.n), "out")        # on the device, the plan's words: poly_gadget_dot_prepared's check
+        _check(self._lib, self._lib.tn_poly_gadget_multidot_prepared_dev(self._h, a.data_ptr(), prepared.tensor.data_ptr(), sets, c.data_ptr(), batch,
+                                                                         outs, terms, int(base_log), GADGET_BALANCED if balanced else 0,
+                                                                         self._stream_ptr(stream)))
+        return self._result(c.reshape(batch, outs, self.n) if host else c, host, one, out)
 
     def cyclic_poly_mult(self, a, b, variant="auto", out=None, stream=None):
         """Untwisted product forward->pointwise->inverse: python_poly_mult (test_ntt_poly_mult.py:38-43)."""
