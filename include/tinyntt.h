@@ -310,6 +310,63 @@ tn_status tn_poly_gadget_multidot_prepared_dev(tn_plan *plan, const void *a, con
                                                size_t outs, size_t terms, uint32_t base_log, uint32_t flags, void *stream);
 
 /*
+ * GALOIS AUTOMORPHISMS: sigma_g : a(x) -> a(x^g) mod (x^n + 1) for odd g, on coefficient rows (tn_automorphism_dev) and on
+ * prepared rows (tn_automorphism_prepared_dev).  Every rotation and conjugation of an RLWE scheme applies one before its key
+ * switch (tn_poly_gadget_multidot_prepared_dev); traces, ring packing and hoisted rotations apply them to prepared rows.
+ *
+ * Definition.  A Galois element is an odd g with 1 <= g < 2n.  For a row a (any word values, taken mod q) sigma_g(a) is the
+ * row out with, for every i < n and t = i g mod 2n:
+ *     out[t]     = a[i] mod q             if t < n,
+ *     out[t - n] = (q - a[i] mod q) mod q otherwise.
+ * Outputs are canonical residues in [0, q); a zero coefficient stays 0 under the negation and never becomes q.  sigma_g is a
+ * ring homomorphism, sigma_g(sigma_h(a)) = sigma_{g h mod 2n}(a), and sigma_1 is canonicalisation.
+ *
+ * tn_automorphism_dev: out[r][m] = sigma_{galois[m]}(a[r]), r < batch, m < count.  a is [batch][n]; out is [batch][count][n];
+ * galois is a HOST array of count elements, read before the call returns.  Works on EVERY plan (general and omega-only plans
+ * included): it needs only n and q.
+ *
+ * tn_automorphism_prepared_dev: the same on PREPARED rows: out[r][m] is the prepared form of sigma_{galois[m]}(the polynomial
+ * whose prepared form is xhat[r]), word for word what tn_prepare_dev writes for sigma_g(tn_unprepare_dev(xhat[r])), for rows
+ * the library wrote.  xhat is [rows][n], out is [rows][count][n].  In the transform domain the automorphism is a permutation of
+ * words (and, where the plan's product runs the base case, one twiddle product on every second word): no transform runs.
+ *
+ * The elements travel by value in the kernel arguments, hence TN_GALOIS_MAX: no device table, no per-plan cache, no copy and no
+ * synchronisation; nothing is set up per g.  count > 1 reads every input row once and writes count images of it (a hoisted
+ * set of rotations, a trace step).  Both calls enqueue on the stream and return, and may be stream-captured.
+ *
+ * Status, in the order checked: TN_EINVAL a NULL plan; TN_EUNSUPPORTED tn_automorphism_prepared_dev on a plan without the
+ * fused kernels (tn_plan_has_fused); TN_EINVAL count outside [1, TN_GALOIS_MAX]; TN_EINVAL an element that is even or >= 2n
+ * (the text names its position); TN_EINVAL batch * count > 2^31 - 1; batch == 0 / rows == 0 succeed and launch nothing;
+ * TN_EINVAL a NULL buffer or a NULL galois; TN_EINVAL out's batch * count rows overlapping the input's batch rows (byte
+ * ranges): the kernels gather, so nothing runs in place.
+ *
+ * When to use which (MI355X, profiles/galois_ab.txt, tools/gpu_galois.py; 9 interleaved repeats, slowest repeat of the new call
+ * against the fastest of the route it replaces; g in {3, 5, 2n - 1, one seeded}):
+ *   - coefficients: tn_automorphism_dev is faster than the torch route (index_select, q - x, where) at every measured point:
+ *     834 - 837 against 4,460 - 6,130 us at n = 4096 / 60-bit, 65,536 rows (x 0.14 - 0.19) and 7.3 - 7.9 against 39.6 - 40.4 us
+ *     at n = 1024 / 24-bit, 4,096 rows (x 0.18 - 0.20).  At n = 4096 it runs at the rate of a device-to-device copy of the same
+ *     rows (5.13 TB/s, x 0.98 of the copy's time); at n = 1024 / 4,096 rows, a launch of 8 us, it takes x 1.9 of the copy's 4.2 us.
+ *   - prepared rows: tn_automorphism_prepared_dev is faster than tn_unprepare_dev + the torch route + tn_prepare_dev at every
+ *     measured point: 729 - 734 against 6,100 - 7,710 us at n = 4096 / 60-bit (x 0.10 - 0.12; base-case format, x 0.86 of the
+ *     copy's time) and 8.6 - 9.0 against 62.5 - 64.9 us at n = 1024 / 24-bit (x 0.13 - 0.14; x 2.1 of the copy's time).  A
+ *     prepared row never needs to leave the transform domain to be rotated.
+ *   - several elements of the same rows: one call with count = 4 against four calls with count = 1 is x 0.65 (coefficients) and
+ *     x 0.79 (prepared) at n = 4096 / 60-bit, x 0.62 and x 0.57 at n = 1024 / 24-bit.  No measured point is slower.
+ *   - beside a key switch: the coefficient automorphism takes x 0.21 (n = 4096 / 60-bit) and x 0.19 (n = 1024 / 24-bit) of one
+ *     tn_poly_gadget_multidot_prepared_dev launch (outs 2, terms 2, shared key) on the same rows.
+ *   - not measured: n = 256, n = 8192, the canonical policy, count above 4.  Not tested: a launch under stream capture; at
+ *     n = 8192 with 64-bit words (an image above 48 KiB) the launcher sets the kernel's dynamic-LDS limit before every launch,
+ *     as the launchers of the fused families do, and that path has never run inside a capture.
+ *
+ * No *_host form, no tn_multi_* form and no cyclic variant (the prepared form serves the negacyclic ring only).  The
+ * reference has no counterpart.
+ */
+#define TN_GALOIS_MAX 16
+tn_status tn_automorphism_dev(tn_plan *plan, const void *a, void *out, size_t batch, const uint32_t *galois, size_t count, void *stream);
+tn_status tn_automorphism_prepared_dev(tn_plan *plan, const void *xhat, void *out, size_t rows, const uint32_t *galois, size_t count,
+                                       void *stream);
+
+/*
  * The *_host entry points cut the batch into chunks that flow H2D -> kernel -> D2H on three
  * streams through a fixed set of device staging slots (copies overlap the kernels when the host
  * buffers are pinned; device staging stays bounded whatever the batch).  rows = rows per chunk,

@@ -63,6 +63,15 @@ struct __attribute__((visibility("hidden"))) ApiCheck {          // (hidden, sta
     if (!outs_) return fail(TN_EINVAL, "outs must be at least 1");
     return outs_ <= 2 || fail(TN_EUNSUPPORTED, "more than 2 output components are not supported");
   }
+  // Galois elements of the automorphism calls: 1 .. TN_GALOIS_MAX of them, each odd and below 2n.  A NULL list is the
+  // buffer check's to refuse (behind batch == 0).
+  bool galois(const uint32_t* g, size_t count) {
+    if (count < 1 || count > TN_GALOIS_MAX) return fail(TN_EINVAL, "count must be between 1 and TN_GALOIS_MAX (16)");
+    for (size_t m = 0; g && m < count; ++m)
+      if (!(g[m] & 1u) || g[m] >= 2 * (uint64_t)v.n)
+        return fail(TN_EINVAL, ("galois[" + std::to_string(m) + "] = " + std::to_string(g[m]) + " is not an odd element below 2n").c_str());
+    return true;
+  }
   // The byte ranges of out_rows rows at out and in_rows rows at in share no byte: the kernels prefetch the next row's input
   // while a row's result is being stored.  Compared as integers: a caller may pass any address, also one near 0.
   bool apart(const void* out, size_t out_rows, const void* in, size_t in_rows, const char* noun) {
@@ -126,6 +135,12 @@ static inline bool check_gadget_multidot(ApiCheck& k, const void* a, const void*
          k.gadget(rows_times(batch, outs), terms, base_log, flags, "batch * outs * terms") && k.work(batch) &&
          k.buffers(a && bhat && c) && k.sets(sets, batch, "bhat_sets", "one set of operands for every row") &&
          k.apart(c, batch * outs, a, batch, "an input") && k.apart(c, batch * outs, bhat, sets * outs * terms, "an input");
+}
+// tn_automorphism_dev and, with the fused() step (prepared), tn_automorphism_prepared_dev: out has batch * count rows.  The
+// kernels gather, so nothing runs in place.
+static inline bool check_automorphism(ApiCheck& k, const void* in, const void* out, size_t batch, const uint32_t* galois, size_t count, bool prepared) {
+  return k.plan() && (!prepared || k.fused()) && k.galois(galois, count) && k.rows(batch, count, "batch * count", "output rows") &&
+         k.work(batch) && k.buffers(in && out && galois) && k.apart(out, batch * count, in, batch, "the input");
 }
 static inline bool check_pointwise(ApiCheck& k, const void* a, const void* b, const void* c, size_t batch) {      // in place is allowed
   return k.plan() && k.rows_wide(batch) && k.buffers(!batch || (a && b && c));

@@ -280,6 +280,22 @@ extern "C" tn_status tn_poly_gadget_multidot_prepared_dev(tn_plan* p, const void
   return TN_OK;
 }
 
+// ---- ring automorphisms a(x) -> a(x^g): count images of every row, the elements by value in the kernel arguments -----------
+extern "C" tn_status tn_automorphism_dev(tn_plan* p, const void* a, void* out, size_t batch, const uint32_t* galois, size_t count, void* stream) {
+  TN_CHECK("tn_automorphism_dev", check_automorphism(k, a, out, batch, galois, count, false));
+  TN_ON_DEVICE(p);
+  TN_HIP(launch_automorphism(p, a, out, batch, galois, count, pick_stream(p, stream)));
+  return TN_OK;
+}
+
+extern "C" tn_status tn_automorphism_prepared_dev(tn_plan* p, const void* xhat, void* out, size_t rows, const uint32_t* galois, size_t count,
+                                                  void* stream) {
+  TN_CHECK("tn_automorphism_prepared_dev", check_automorphism(k, xhat, out, rows, galois, count, true));
+  TN_ON_DEVICE(p);
+  TN_HIP(launch_automorphism_prepared(p, xhat, out, rows, galois, count, pick_stream(p, stream)));
+  return TN_OK;
+}
+
 extern "C" tn_status tn_pointwise_mul_dev(tn_plan* p, const void* a, const void* b, void* c, size_t batch, void* stream) {
   TN_CHECK("tn_pointwise_mul_dev", check_pointwise(k, a, b, c, batch));
   TN_ON_DEVICE(p);

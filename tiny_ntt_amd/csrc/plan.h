@@ -174,7 +174,8 @@ inline hipError_t launch_persistent(const tn_plan* p, hipStream_t s, const void*
   return le;
 }
 
-// kernels.hip (prepared operand: kernels_prepared.hip; transform domain: kernels_hat.hip; gadget: kernels_gadget.hip)
+// kernels.hip (prepared operand: kernels_prepared.hip; transform domain: kernels_hat.hip; gadget: kernels_gadget.hip;
+// automorphisms: kernels_galois.hip)
 bool fused_supported(u32 logn, int elem_bytes);
 const char* fused_kernel_name(const tn_plan* p);
 const char* cg_kernel_name(const tn_plan* p, int group, int layout);
@@ -200,6 +201,11 @@ hipError_t launch_polydot_gadget(const tn_plan* p, const void* a, const void* bh
 // c[r][o] = sum_j digit_j(a[r]) * b[shared ? 0 : r][o][j], o < 2
 hipError_t launch_polydot_gadget2(const tn_plan* p, const void* a, const void* bhat, bool shared, void* c, size_t batch, size_t terms,
                                   tn::u32 base_log, bool balanced, hipStream_t s);
+// ring automorphisms a(x) -> a(x^g) (kernels_galois.hip): count images of every row, out[r][m] = sigma_{galois[m]}(row r); on
+// coefficient rows (tn_automorphism_dev: every plan) and on prepared rows (tn_automorphism_prepared_dev: fused plans only)
+hipError_t launch_automorphism(const tn_plan* p, const void* a, void* out, size_t batch, const uint32_t* galois, size_t count, hipStream_t s);
+hipError_t launch_automorphism_prepared(const tn_plan* p, const void* xhat, void* out, size_t rows, const uint32_t* galois, size_t count,
+                                        hipStream_t s);
 hipError_t launch_cg(const tn_plan* p, int mode, int group, int layout, const void* a, const void* b, void* out,
                      void* trace, size_t batch, hipStream_t s);
 hipError_t launch_pointwise(const tn_plan* p, const void* a, const void* b, void* c, size_t batch, hipStream_t s);

@@ -31,6 +31,7 @@ VARIANTS = {"auto": VARIANT_AUTO, "fused": VARIANT_FUSED, "cg": VARIANT_CG, "cg8
             "cg_swizzled": 5, "cg8_swizzled": 6, "cg2": 7, "cg2_padded": 8, "cg2_swizzled": 9, "cg4": 10, "cg4_padded": 11, "cg4_swizzled": 12}
 CG_VARIANTS = tuple(k for k in VARIANTS if k.startswith("cg"))
 PLAN_FORCE_CANONICAL = 1
+GALOIS_MAX = 16               # Galois elements per automorphism call: include/tinyntt.h TN_GALOIS_MAX
 GADGET_BALANCED = 1           # digits in [-B/2, B/2): include/tinyntt.h TN_GADGET_BALANCED
 PLAN_CANONICAL_INPUTS = 2     # the caller promises inputs in [0, q): include/tinyntt.h TN_PLAN_CANONICAL_INPUTS
 
@@ -41,6 +42,7 @@ EXPORTED_SYMBOLS = (
     "tn_poly_mult_dev", "tn_poly_mult_host", "tn_plan_set_host_chunk_rows", "tn_cyclic_poly_mult_dev", "tn_pointwise_mul_dev", "tn_schoolbook_dev",
     "tn_prepare_dev", "tn_poly_mult_prepared_dev", "tn_poly_dot_prepared_dev", "tn_unprepare_dev", "tn_poly_dot_hat_dev",
     "tn_gadget_decompose_dev", "tn_poly_gadget_dot_prepared_dev", "tn_poly_gadget_multidot_prepared_dev",
+    "tn_automorphism_dev", "tn_automorphism_prepared_dev",
     "tn_plan_export_table", "tn_ntt_forward_dev", "tn_ntt_inverse_dev",
     "tn_ntt_forward_host", "tn_ntt_inverse_host", "tn_ntt_forward_trace_host", "tn_twisted_ntt_forward_dev",
     "tn_twisted_ntt_forward_host", "tn_schoolbook_host",
@@ -101,6 +103,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.tn_gadget_decompose_dev.argtypes = [vp, vp, vp, sz, sz, u32, u32, vp]
     lib.tn_poly_gadget_dot_prepared_dev.argtypes = [vp, vp, vp, sz, vp, sz, sz, u32, u32, vp]
     lib.tn_poly_gadget_multidot_prepared_dev.argtypes = [vp, vp, vp, sz, vp, sz, sz, sz, u32, u32, vp]
+    lib.tn_automorphism_dev.argtypes = [vp, vp, vp, sz, ctypes.POINTER(u32), sz, vp]
+    lib.tn_automorphism_prepared_dev.argtypes = [vp, vp, vp, sz, ctypes.POINTER(u32), sz, vp]
     lib.tn_schoolbook_dev.argtypes = [vp, vp, vp, vp, sz, vp]
     lib.tn_plan_export_table.argtypes = [vp, ci, vp]
     for name in ("tn_ntt_forward_dev", "tn_ntt_inverse_dev", "tn_twisted_ntt_forward_dev"):
@@ -489,6 +493,56 @@ class Plan:
                                                                          outs, terms, int(base_log), GADGET_BALANCED if balanced else 0,
                                                                          self._stream_ptr(stream)))
         return self._result(c.reshape(batch, outs, self.n) if host else c, host, one, out)
+
+    # ---- ring automorphisms a(x) -> a(x^g) ----------------------------------------
+    @staticmethod
+    def _galois(galois):
+        """galois, an int or a sequence of ints -> (ctypes uint32 array, count, one element was given).  Values the C ABI's
+        uint32 cannot hold are refused here; evenness and the range [1, 2n) are the library's to check."""
+        one = isinstance(galois, (int, np.integer))
+        vals = [int(galois)] if one else [int(g) for g in galois]
+        if any(g < 0 or g >= 2 ** 32 for g in vals):
+            raise ValueError("Galois elements must be odd integers in [1, 2n)")
+        return (ctypes.c_uint32 * max(len(vals), 1))(*vals), len(vals), one
+
+    def _images(self, out, batch, count, device):
+        """out, or a new tensor on `device`: batch x count rows of the plan's words, contiguous."""
+        import torch
+        c = out if out is not None else torch.empty((batch, count, self.n), dtype=self.torch_dtype, device=device)
+        if not _is_torch(c) or c.numel() != batch * count * self.n or not c.is_contiguous() or c.shape[-1] != self.n:
+            raise ValueError(f"Expected an output of {batch} x {count} rows of {self.n} coefficients")
+        self._dev_rows(c.reshape(batch * count, self.n), "out")
+        return c
+
+    def automorphism(self, a, galois, out=None, stream=None):
+        """sigma_g(a[r]) = a[r](x^g) mod (x^n + 1) for every Galois element g given (tn_automorphism_dev; include/tinyntt.h has
+        the definition): a is (batch, n) or (n,), host values (taken mod q) or a device tensor of any words; galois is an odd
+        int in [1, 2n) or a sequence of up to GALOIS_MAX of them.  Returns canonical residues, (batch, n) for an int and
+        (batch, count, n) for a sequence, one read of a for all of them.  Works on every plan."""
+        a, batch, host, one = self._rows_in(a)
+        gl, count, single = self._galois(galois)
+        c = self._images(out, batch, count, a.device)
+        _check(self._lib, self._lib.tn_automorphism_dev(self._h, a.data_ptr(), c.data_ptr(), batch, gl, count, self._stream_ptr(stream)))
+        if out is None:
+            c = c.reshape(batch, self.n) if single else c.reshape(batch, count, self.n)
+        return self._result(c, host, one, out)
+
+    def automorphism_prepared(self, prepared: PreparedOperand, galois, out=None, stream=None) -> PreparedOperand:
+        """The prepared form of sigma_g of the polynomials `prepared` holds (tn_automorphism_prepared_dev): a permutation of words
+        in the transform domain, no transform runs.  Returns a PreparedOperand of rows * count rows, row r's image under element
+        m at row r * count + m; word for word prepare(automorphism(unprepare(prepared), galois))."""
+        self._own_prepared(prepared, "automorphism_prepared", "operand")
+        gl, count, _ = self._galois(galois)
+        rows = prepared.rows
+        if isinstance(out, PreparedOperand):      # written in place of a new tensor: this plan's, rows * count rows
+            self._own_prepared(out, "automorphism_prepared", "output")
+            if out.rows != rows * count:
+                raise ValueError(f"Expected an output of {rows} x {count} rows of {self.n} coefficients")
+            out = out.tensor
+        c = self._images(out, rows, count, prepared.tensor.device)
+        _check(self._lib, self._lib.tn_automorphism_prepared_dev(self._h, prepared.tensor.data_ptr(), c.data_ptr(), rows, gl, count,
+                                                                 self._stream_ptr(stream)))
+        return PreparedOperand(self, c.reshape(rows * count, self.n), rows * count)
 
     def cyclic_poly_mult(self, a, b, variant="auto", out=None, stream=None):
         """Untwisted product forward->pointwise->inverse: python_poly_mult (test_ntt_poly_mult.py:38-43)."""

@@ -44,6 +44,16 @@ def sqrt_mod(a: int, p: int):
     return r
 
 
+def galois_element(n: int, step: int = 0, conjugate: bool = False) -> int:
+    """The Galois element of a rotation by `step` slots, 5^step mod 2n (a negative step gives the inverse), times 2n - 1 with
+    `conjugate`: the odd g that Plan.automorphism / Plan.automorphism_prepared take (include/tinyntt.h: sigma_g)."""
+    m = 2 * int(n)
+    g = pow(5, int(step), m)          # (Python >= 3.8: a negative exponent is the modular inverse's power)
+    if conjugate:
+        g = g * (m - 1) % m
+    return g
+
+
 def psi_from_omega(omega: int, n: int, q: int) -> int:
     """A primitive 2n-th root psi with psi^2 == omega (needed because plans are keyed on psi).
 
