@@ -310,6 +310,54 @@ tn_status tn_poly_gadget_multidot_prepared_dev(tn_plan *plan, const void *a, con
                                                size_t outs, size_t terms, uint32_t base_log, uint32_t flags, void *stream);
 
 /*
+ * EXTERNAL PRODUCT RGSW x RLWE: both output components from the digits of ALL input polynomials of a ciphertext in ONE launch,
+ * the inner loop of a CMux, a blind rotation (FHEW, TFHE, LMKCDEY) and a GSW-style multiplication.  The two calls above cut the
+ * digits of one polynomial per output row; this one cuts the digits of every component of (a_0, ..., a_{ins-1}) and multiplies
+ * all ins * terms digit rows into every output component.
+ *
+ * tn_poly_external_product_prepared_dev: c[r][o] = sum_{i < ins} sum_{j < terms} digit_j(a[r][i]) * b[s][o][i][j] in
+ * Z_q[x]/(x^n+1), s = (bhat_sets == 1 ? 0 : r), r < batch, o < outs.  a is [batch][ins][n], any word values, taken mod q; bhat
+ * is [bhat_sets][outs][ins][terms][n] as tn_prepare_dev wrote it for that many rows of b; c is [batch][outs][n], canonical
+ * residues.  With this layout bhat + o * ins * terms * n of a shared set is a valid shared set of tn_poly_dot_prepared_dev with
+ * ins * terms terms, and for ins == 1 the layout is exactly tn_poly_gadget_multidot_prepared_dev's.  Digits, flags and base_log
+ * are those of tn_poly_gadget_dot_prepared_dev; balanced carries start at 0 for every input polynomial and never run from one
+ * polynomial into the next.
+ * The result is BIT-IDENTICAL, component by component, to tn_poly_dot_prepared_dev with ins * terms terms on the digits that
+ * tn_gadget_decompose_dev writes for a viewed as batch * ins rows ([batch * ins][terms][n] = [batch][ins * terms][n]) and
+ * component o's [sets][ins * terms][n] slice of bhat.
+ *   ins == 1             is tn_poly_gadget_multidot_prepared_dev and runs its kernels.
+ *   ins >= 2, outs == 2  runs a kernel of its own: ins * terms forward transforms and two inverses per output row, nothing but a
+ *                        read and c written; ins is a run-time count (ins = 3, a rank-2 module, works like ins = 2).
+ *   ins >= 2, outs == 1  is NOT SUPPORTED (TN_EUNSUPPORTED): tn_gadget_decompose_dev on the batch * ins rows followed by
+ *                        tn_poly_dot_prepared_dev with ins * terms terms serves it.
+ *
+ * When to use which (MI355X, profiles/extprod_ab.txt; ins = outs = 2, balanced digits, terms 2 - 4, 9 interleaved repeats; the
+ * slowest repeat of the one launch against the fastest repeat of the faster of two routes on the same buffers: route A, one
+ * tn_poly_gadget_multidot_prepared_dev launch per input polynomial and a modular addition of the two results; route B,
+ * tn_gadget_decompose_dev and one tn_poly_dot_prepared_dev launch per component):
+ *   - ins >= 2, both components wanted: the one launch is faster at every measured point by disjoint ranges, x 0.55 - 0.61 of the
+ *     faster route at n = 4096 / 60-bit, 65,536 rows (6,916 us against route B's 12,164 us at two terms, shared key; the key per
+ *     row at four terms was measured at 32,768 rows) and x 0.59 - 0.60 at n = 1024 / 24-bit, 4,096 rows.  Route B is the faster
+ *     route at two and three terms, route A at four terms of n = 4096.  No measured point is slower or within the spread.
+ *   - route A's two launches WITHOUT their addition still cost more: the one launch is x 0.83 - 0.90 of them at n = 4096 and
+ *     x 0.77 - 0.86 at n = 1024; the addition in torch costs about as much again as the launches at two terms.
+ *   - one input polynomial: ins = 1 is tn_poly_gadget_multidot_prepared_dev, at its cost.
+ *   - n = 256, n = 8192, the canonical policy and ins = 3 were not measured.
+ *
+ * Status, in this order: TN_EINVAL for a NULL plan; TN_EUNSUPPORTED for a plan without the fused kernels; TN_EINVAL for
+ * ins == 0; TN_EINVAL for outs == 0 and TN_EUNSUPPORTED for outs > 2; TN_EUNSUPPORTED for ins >= 2 with outs == 1; TN_EINVAL
+ * for everything the gadget calls refuse (terms == 0, a flag bit other than TN_GADGET_BALANCED, base_log == 0 or
+ * 2^base_log >= q, (terms - 1) * base_log >= 64, batch * outs * ins * terms > 2^31 - 1); batch == 0 succeeds and launches
+ * nothing; TN_EINVAL for a NULL buffer, for bhat_sets neither 1 nor batch, and for c's batch * outs rows overlapping a's
+ * batch * ins rows or bhat's bhat_sets * outs * ins * terms rows (byte ranges).  The call enqueues on the stream and returns,
+ * and may be stream-captured (a captured launch hands rows out at the fixed stride).  No cyclic variant, no *_host form and
+ * no tn_multi_* form.
+ */
+tn_status tn_poly_external_product_prepared_dev(tn_plan *plan, const void *a, const void *bhat, size_t bhat_sets, void *c,
+                                                size_t batch, size_t ins, size_t outs, size_t terms, uint32_t base_log,
+                                                uint32_t flags, void *stream);
+
+/*
  * GALOIS AUTOMORPHISMS: sigma_g : a(x) -> a(x^g) mod (x^n + 1) for odd g, on coefficient rows (tn_automorphism_dev) and on
  * prepared rows (tn_automorphism_prepared_dev).  Every rotation and conjugation of an RLWE scheme applies one before its key
  * switch (tn_poly_gadget_multidot_prepared_dev); traces, ring packing and hoisted rotations apply them to prepared rows.

@@ -63,6 +63,13 @@ struct __attribute__((visibility("hidden"))) ApiCheck {          // (hidden, sta
     if (!outs_) return fail(TN_EINVAL, "outs must be at least 1");
     return outs_ <= 2 || fail(TN_EUNSUPPORTED, "more than 2 output components are not supported");
   }
+  // input polynomials of tn_poly_external_product_prepared_dev: one is the multidot call; two or more run the kernel built for
+  // two output components
+  bool ins(size_t ins_) { return ins_ || fail(TN_EINVAL, "ins must be at least 1"); }
+  bool ins_outs(size_t ins_, size_t outs_) {
+    return !(ins_ >= 2 && outs_ == 1) ||
+           fail(TN_EUNSUPPORTED, "2 or more input polynomials into 1 output component are not supported (tn_gadget_decompose_dev, then tn_poly_dot_prepared_dev)");
+  }
   // Galois elements of the automorphism calls: 1 .. TN_GALOIS_MAX of them, each odd and below 2n.  A NULL list is the
   // buffer check's to refuse (behind batch == 0).
   bool galois(const uint32_t* g, size_t count) {
@@ -125,8 +132,13 @@ static inline bool check_gadget_dot(ApiCheck& k, const void* a, const void* bhat
          k.sets(sets, batch, "bhat_sets", "one set of operands for every row") && k.apart(c, batch, a, batch, "an input") &&
          k.apart(c, batch, bhat, sets * terms, "an input");
 }
-// batch * outs for a row limit; a batch that is above the limit by itself stands as it is (times outs it could wrap size_t)
-static inline size_t rows_times(size_t batch, size_t outs) { return batch > 0x7fffffffull ? batch : batch * outs; }
+// batch * outs for a row limit; a factor that is above the limit by itself stands as it is (times the other it could wrap
+// size_t), unless the other is 0
+static inline size_t rows_times(size_t batch, size_t outs) {
+  const size_t max = 0x7fffffffull;
+  if (!batch || !outs) return 0;
+  return batch > max ? batch : outs > max ? outs : batch * outs;
+}
 // check_gadget_dot's list with the component count behind the plan's: the row limit holds for batch * outs * terms, c has
 // batch * outs rows and bhat sets * outs * terms
 static inline bool check_gadget_multidot(ApiCheck& k, const void* a, const void* bhat, size_t sets, const void* c, size_t batch, size_t outs,
@@ -135,6 +147,16 @@ static inline bool check_gadget_multidot(ApiCheck& k, const void* a, const void*
          k.gadget(rows_times(batch, outs), terms, base_log, flags, "batch * outs * terms") && k.work(batch) &&
          k.buffers(a && bhat && c) && k.sets(sets, batch, "bhat_sets", "one set of operands for every row") &&
          k.apart(c, batch * outs, a, batch, "an input") && k.apart(c, batch * outs, bhat, sets * outs * terms, "an input");
+}
+// check_gadget_multidot's list with the count of input polynomials behind the plan's: the row limit holds for
+// batch * outs * ins * terms (each factor of rows_times is below 2^31 or the product stands above it: no step wraps size_t), a
+// has batch * ins rows, c batch * outs and bhat sets * outs * ins * terms
+static inline bool check_external_product(ApiCheck& k, const void* a, const void* bhat, size_t sets, const void* c, size_t batch, size_t ins,
+                                          size_t outs, size_t terms, uint32_t base_log, uint32_t flags) {
+  return k.plan() && k.fused() && k.ins(ins) && k.outs(outs) && k.ins_outs(ins, outs) &&
+         k.gadget(rows_times(rows_times(batch, outs), ins), terms, base_log, flags, "batch * outs * ins * terms") && k.work(batch) &&
+         k.buffers(a && bhat && c) && k.sets(sets, batch, "bhat_sets", "one set of operands for every row") &&
+         k.apart(c, batch * outs, a, batch * ins, "an input") && k.apart(c, batch * outs, bhat, sets * outs * ins * terms, "an input");
 }
 // tn_automorphism_dev and, with the fused() step (prepared), tn_automorphism_prepared_dev: out has batch * count rows.  The
 // kernels gather, so nothing runs in place.

@@ -280,6 +280,18 @@ extern "C" tn_status tn_poly_gadget_multidot_prepared_dev(tn_plan* p, const void
   return TN_OK;
 }
 
+// the external product: one input polynomial is the multidot call; two or more into two components run polydot_extprod_kernel
+extern "C" tn_status tn_poly_external_product_prepared_dev(tn_plan* p, const void* a, const void* bhat, size_t bhat_sets, void* c, size_t batch,
+                                                           size_t ins, size_t outs, size_t terms, uint32_t base_log, uint32_t flags, void* stream) {
+  TN_CHECK("tn_poly_external_product_prepared_dev", check_external_product(k, a, bhat, bhat_sets, c, batch, ins, outs, terms, base_log, flags));
+  TN_ON_DEVICE(p);
+  const bool balanced = (flags & TN_GADGET_BALANCED) != 0, shared = bhat_sets == 1;
+  if (ins >= 2) TN_HIP(launch_polydot_extprod(p, a, bhat, shared, c, batch, ins, terms, base_log, balanced, pick_stream(p, stream)));
+  else if (outs == 1) TN_HIP(launch_polydot_gadget(p, a, bhat, shared, c, batch, terms, base_log, balanced, pick_stream(p, stream)));
+  else TN_HIP(launch_polydot_gadget2(p, a, bhat, shared, c, batch, terms, base_log, balanced, pick_stream(p, stream)));
+  return TN_OK;
+}
+
 // ---- ring automorphisms a(x) -> a(x^g): count images of every row, the elements by value in the kernel arguments -----------
 extern "C" tn_status tn_automorphism_dev(tn_plan* p, const void* a, void* out, size_t batch, const uint32_t* galois, size_t count, void* stream) {
   TN_CHECK("tn_automorphism_dev", check_automorphism(k, a, out, batch, galois, count, false));

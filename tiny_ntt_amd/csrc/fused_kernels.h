@@ -6,6 +6,7 @@
 //   kernels_prepared.hip  prepared operand: prepare, the product and the dot product with b prepared
 //   kernels_hat.hip       transform domain: both operands prepared; unprepare
 //   kernels_gadget.hip    gadget decomposition and the dot product that decomposes a itself
+//   kernels_extprod.hip   external product: the digits of all input polynomials of a row into both output components
 #pragma once
 #include <hip/hip_runtime.h>
 #include <type_traits>
@@ -387,6 +388,21 @@ template <typename Sh>
 constexpr size_t fused_lds_bytes(int tables, size_t extra_elems = 0) {
   typedef typename Sh::Cfg Cfg;
   return ((size_t)Cfg::lds_elems() + extra_elems) * sizeof(typename Sh::E) + (size_t)tables * Cfg::lds_tw_count() * sizeof(typename TwOf<typename Sh::E>::type) + 16;
+}
+
+// Words of a per thread that the kernels with two sums (polydot_gadget2_kernel, polydot_extprod_kernel) keep in LDS instead of
+// registers: as many as the CU's LDS holds without a resident workgroup fewer than the gadget kernel's.
+constexpr size_t GADGET2_CU_LDS = 160 * 1024;
+template <typename Sh> constexpr int gadget2_lds_words() {
+  typedef typename Sh::Cfg Cfg;
+  const size_t base = fused_lds_bytes<Sh>(2), word_row = (size_t)Cfg::THREADS * sizeof(typename Sh::E);
+  const size_t waves = (size_t)(Cfg::THREADS + 63) / 64, by_waves = 4 * (size_t)dot_waves<typename Sh::E, Sh::LOGN, Sh::LPT, Sh::LAZY>() / waves;
+  size_t wgs = GADGET2_CU_LDS / base;        // resident workgroups of the gadget kernel: what LDS holds, what the waves allow, one at least
+  if (wgs > by_waves) wgs = by_waves;
+  if (wgs < 1) wgs = 1;
+  int x = Cfg::R;
+  while (x > 0 && GADGET2_CU_LDS / (base + (size_t)x * word_row) < wgs) --x;
+  return x;
 }
 
 }  // namespace tn

@@ -195,27 +195,14 @@ hipError_t launch_polydot_gadget(const tn_plan* p, const void* a, const void* bh
 // component 0 is requested before the forward, as in the gadget kernel; the row of component 1 goes pair by pair into the
 // registers component 0's product has finished with (polydot_hat_kernel's base case does the same).  The words of a, the
 // gadget kernel's fourth row, stay in LDS, thread-private at [r * THREADS + tau], and are read back once per term at the
-// digit cut: XL words per thread there, the rest in registers (gadget2_lds_words: as many as the CU's LDS holds without a
-// resident workgroup fewer than the gadget kernel's).
+// digit cut: XL words per thread there, the rest in registers (gadget2_lds_words, fused_kernels.h: as many as the CU's LDS holds
+// without a resident workgroup fewer than the gadget kernel's).
 // The inverse's private twiddles: the first inverse's are requested behind the term loop, the second inverse's behind the
 // first result's stores, the next row's words of a inside the second inverse (inverse_all's callback).  Requests that could be
 // formed from one thread index go through copies of their own (opaque_copy): formed from the term's, the addresses of
 // component 1's row and the second inverse's records (which ARE the first inverse's) were kept in registers across the
 // transforms, 16 - 32 of them.  Everything else is polydot_gadget_kernel's.  All 50 instantiations hold 128 registers without
 // scratch at the gadget kernel's waves per SIMD (DESIGN.md 3.2e has the report).
-constexpr size_t GADGET2_CU_LDS = 160 * 1024;
-template <typename Sh> constexpr int gadget2_lds_words() {
-  typedef typename Sh::Cfg Cfg;
-  const size_t base = fused_lds_bytes<Sh>(2), word_row = (size_t)Cfg::THREADS * sizeof(typename Sh::E);
-  const size_t waves = (size_t)(Cfg::THREADS + 63) / 64, by_waves = 4 * (size_t)dot_waves<typename Sh::E, Sh::LOGN, Sh::LPT, Sh::LAZY>() / waves;
-  size_t wgs = GADGET2_CU_LDS / base;        // resident workgroups of the gadget kernel: what LDS holds, what the waves allow, one at least
-  if (wgs > by_waves) wgs = by_waves;
-  if (wgs < 1) wgs = 1;
-  int x = Cfg::R;
-  while (x > 0 && GADGET2_CU_LDS / (base + (size_t)x * word_row) < wgs) --x;
-  return x;
-}
-
 template <typename E, int LOGN, int LPT, bool LAZY, bool BC, bool SHARED, int XL>
 __global__ void __launch_bounds__((1 << (LOGN - LPT)), (dot_waves<E, LOGN, LPT, LAZY>()))
 polydot_gadget2_kernel(const Arith<E> ar, const typename TwOf<E>::type* __restrict__ tab_fwd,

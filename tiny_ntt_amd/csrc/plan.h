@@ -175,7 +175,7 @@ inline hipError_t launch_persistent(const tn_plan* p, hipStream_t s, const void*
 }
 
 // kernels.hip (prepared operand: kernels_prepared.hip; transform domain: kernels_hat.hip; gadget: kernels_gadget.hip;
-// automorphisms: kernels_galois.hip)
+// automorphisms: kernels_galois.hip; external product: kernels_extprod.hip)
 bool fused_supported(u32 logn, int elem_bytes);
 const char* fused_kernel_name(const tn_plan* p);
 const char* cg_kernel_name(const tn_plan* p, int group, int layout);
@@ -200,6 +200,10 @@ hipError_t launch_polydot_gadget(const tn_plan* p, const void* a, const void* bh
 // ... with two output components from one forward transform per term (tn_poly_gadget_multidot_prepared_dev, outs == 2):
 // c[r][o] = sum_j digit_j(a[r]) * b[shared ? 0 : r][o][j], o < 2
 hipError_t launch_polydot_gadget2(const tn_plan* p, const void* a, const void* bhat, bool shared, void* c, size_t batch, size_t terms,
+                                  tn::u32 base_log, bool balanced, hipStream_t s);
+// external product (kernels_extprod.hip; tn_poly_external_product_prepared_dev, ins >= 2 and outs == 2): the digits of all `ins`
+// input polynomials of a row into both components, c[r][o] = sum_i sum_j digit_j(a[r][i]) * b[shared ? 0 : r][o][i][j], o < 2
+hipError_t launch_polydot_extprod(const tn_plan* p, const void* a, const void* bhat, bool shared, void* c, size_t batch, size_t ins, size_t terms,
                                   tn::u32 base_log, bool balanced, hipStream_t s);
 // ring automorphisms a(x) -> a(x^g) (kernels_galois.hip): count images of every row, out[r][m] = sigma_{galois[m]}(row r); on
 // coefficient rows (tn_automorphism_dev: every plan) and on prepared rows (tn_automorphism_prepared_dev: fused plans only)

@@ -42,6 +42,7 @@ EXPORTED_SYMBOLS = (
     "tn_poly_mult_dev", "tn_poly_mult_host", "tn_plan_set_host_chunk_rows", "tn_cyclic_poly_mult_dev", "tn_pointwise_mul_dev", "tn_schoolbook_dev",
     "tn_prepare_dev", "tn_poly_mult_prepared_dev", "tn_poly_dot_prepared_dev", "tn_unprepare_dev", "tn_poly_dot_hat_dev",
     "tn_gadget_decompose_dev", "tn_poly_gadget_dot_prepared_dev", "tn_poly_gadget_multidot_prepared_dev",
+    "tn_poly_external_product_prepared_dev",
     "tn_automorphism_dev", "tn_automorphism_prepared_dev",
     "tn_plan_export_table", "tn_ntt_forward_dev", "tn_ntt_inverse_dev",
     "tn_ntt_forward_host", "tn_ntt_inverse_host", "tn_ntt_forward_trace_host", "tn_twisted_ntt_forward_dev",
@@ -103,6 +104,7 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.tn_gadget_decompose_dev.argtypes = [vp, vp, vp, sz, sz, u32, u32, vp]
     lib.tn_poly_gadget_dot_prepared_dev.argtypes = [vp, vp, vp, sz, vp, sz, sz, u32, u32, vp]
     lib.tn_poly_gadget_multidot_prepared_dev.argtypes = [vp, vp, vp, sz, vp, sz, sz, sz, u32, u32, vp]
+    lib.tn_poly_external_product_prepared_dev.argtypes = [vp, vp, vp, sz, vp, sz, sz, sz, sz, u32, u32, vp]
     lib.tn_automorphism_dev.argtypes = [vp, vp, vp, sz, ctypes.POINTER(u32), sz, vp]
     lib.tn_automorphism_prepared_dev.argtypes = [vp, vp, vp, sz, ctypes.POINTER(u32), sz, vp]
     lib.tn_schoolbook_dev.argtypes = [vp, vp, vp, vp, sz, vp]
@@ -492,6 +494,42 @@ class Plan:
         _check(self._lib, self._lib.tn_poly_gadget_multidot_prepared_dev(self._h, a.data_ptr(), prepared.tensor.data_ptr(), sets, c.data_ptr(), batch,
                                                                          outs, terms, int(base_log), GADGET_BALANCED if balanced else 0,
                                                                          self._stream_ptr(stream)))
+        return self._result(c.reshape(batch, outs, self.n) if host else c, host, one, out)
+
+    def poly_external_product_prepared(self, a, prepared: PreparedOperand, outs, terms, base_log, balanced=False, out=None, stream=None):
+        """c[r][o] = sum_i sum_j digit_j(a[r][i]) * b[r][o][i][j] for o < outs (tn_poly_external_product_prepared_dev): the external
+        product RGSW x RLWE from ONE launch, the digits of every input polynomial cut and transformed once for both components.
+        a is (batch, ins, n), or (ins, n) for one ciphertext, host values or a device tensor; the prepared operand has
+        batch * outs * ins * terms rows ([batch][outs][ins][terms]), or outs * ins * terms rows that every output row is
+        multiplied by.  ins >= 2 needs outs == 2; ins == 1 is poly_gadget_multidot_prepared.  Returns (batch, outs, n) or
+        (outs, n), bit-identical per component to poly_dot_prepared on gadget_decompose of the (batch * ins, n) view of a."""
+        import torch
+        self._own_prepared(prepared, "poly_external_product_prepared", "second operand")
+        host = not _is_torch(a)
+        if host:
+            a = np.asarray(a)
+        if a.ndim not in (2, 3) or a.shape[-1] != self.n or a.shape[-2] == 0:
+            raise ValueError(f"Expected a of shape (batch, ins, {self.n}) or (ins, {self.n})")
+        one = a.ndim == 2
+        ins = int(a.shape[-2])
+        batch = 1 if one else int(a.shape[0])
+        if host:
+            a = self.to_device(a.reshape(batch * ins, self.n))
+        else:
+            if not a.is_contiguous():
+                raise TinyNttError(TN_EINVAL, f"a: need a contiguous tensor of {self.elem_bytes}-byte integers")
+            self._dev_rows(a.reshape(batch * ins, self.n), "a")
+        outs, terms = int(outs), int(terms)
+        if terms < 1 or outs < 1:
+            raise ValueError(f"Expected terms >= 1 and outs >= 1, got {terms} and {outs}")
+        sets = self._sets(prepared, batch, outs * ins * terms)
+        c = out if out is not None else torch.empty((batch, outs, self.n), dtype=self.torch_dtype, device=a.device)
+        if not _is_torch(c) or c.numel() != batch * outs * self.n or not c.is_contiguous():
+            raise ValueError(f"Expected an output of {batch} x {outs} rows of {self.n} coefficients")
+        self._dev_rows(c.reshape(batch * outs, self.n), "out")        # on the device, the plan's words: poly_gadget_dot_prepared's check
+        _check(self._lib, self._lib.tn_poly_external_product_prepared_dev(self._h, a.data_ptr(), prepared.tensor.data_ptr(), sets, c.data_ptr(), batch,
+                                                                          ins, outs, terms, int(base_log), GADGET_BALANCED if balanced else 0,
+                                                                          self._stream_ptr(stream)))
         return self._result(c.reshape(batch, outs, self.n) if host else c, host, one, out)
 
     # ---- ring automorphisms a(x) -> a(x^g) ----------------------------------------
