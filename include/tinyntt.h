@@ -358,6 +358,76 @@ tn_status tn_poly_external_product_prepared_dev(tn_plan *plan, const void *a, co
                                                 uint32_t flags, void *stream);
 
 /*
+ * CMUX ROTATION STEP: one step of a blind rotation (FHEW, TFHE, LMKCDEY) on an accumulator ciphertext acc = (acc_0, acc_1),
+ *     acc  <-  acc + RGSW(s_i) [x] ((X^e - 1) * acc),        e = the step's LWE coefficient, another one for every ciphertext,
+ * as the explicit pieces (tn_monomial_mul_dev, then tn_poly_external_product_prepared_dev, then an addition) or from ONE launch
+ * (tn_poly_cmux_rotate_prepared_dev): the rotation is an address offset and a sign on the load the kernel performs anyway, and
+ * the unrotated words that "- acc" needs are the ones the addition at the store needs.  No transform is added: 2 * terms + 2
+ * per row, as in the external product.
+ *
+ * Definition.  exps is a DEVICE array of batch 32-bit words; any value is taken mod 2n: e = exps[r] & (2n - 1).  For a row x
+ * (any word values, taken mod q) and t < n let s = (t - e) mod 2n; then
+ *     rot_e(x)[t] = x[s] mod q                      if s < n,
+ *                 = (q - x[s - n] mod q) mod q      otherwise      (a zero stays 0, never q).
+ * rot_e(x) is X^e * x in Z_q[x]/(x^n + 1); rot_0 is canonicalisation, rot_n is negation.
+ *
+ * tn_monomial_mul_dev: a and out are [batch][group][n]; exponent exps[r] applies to all `group` rows of item r (group = 2 for
+ * an RLWE ciphertext).  flags == 0: out = rot_e(a), that is X^e * a.  TN_MONOMIAL_MINUS_ONE: out = (rot_e(a) - a) mod q, that is
+ * (X^e - 1) * a.  Outputs are canonical residues.  An element-wise kernel on EVERY plan (general and omega-only plans
+ * included): it needs only n and q.  Stores are unit-stride, loads are unit-stride apart from the one wrap.  The index is
+ * masked to the row: NO CONTENT OF exps CAN CAUSE AN OUT-OF-BOUNDS ACCESS (the same holds for the fused call).
+ *
+ * exps is read by the kernel, not by the host: a CAPTURED launch sees the exponents that are in the buffer at REPLAY time.  A
+ * blind rotation replays one graph with new exponents written into the same buffer.
+ *
+ * tn_poly_cmux_rotate_prepared_dev:
+ *     c[r][o] = ( a[r][o] mod q + sum_{i < comps} sum_{j < terms} digit_j( ((X^{e_r} - 1) * a[r][i]) ) * b[s][o][i][j] ) mod q,
+ * o < comps, s = (bhat_sets == 1 ? 0 : r), r < batch.  a and c are [batch][comps][n]; bhat is [bhat_sets][comps][comps][terms][n],
+ * exactly the layout of tn_poly_external_product_prepared_dev with ins = outs = comps; exps as above.  Digits, base_log and
+ * flags (TN_GADGET_BALANCED) are the gadget calls'; carries start at 0 for every input polynomial.  comps must be 2 (the
+ * kernel has two output components).
+ * The result is BIT-IDENTICAL to the explicit route on the same buffers: tn_monomial_mul_dev(group = 2, TN_MONOMIAL_MINUS_ONE),
+ * tn_poly_external_product_prepared_dev(ins = 2, outs = 2) on its output, then word-wise (a mod q + .) mod q.
+ * c must not overlap a or bhat (byte ranges): the call does not run in place.  A blind rotation alternates two accumulator
+ * buffers, acc -> acc' -> acc.
+ *
+ * When to use which (MI355X, profiles/cmux_ab.txt, tools/gpu_cmux.py; balanced digits, terms 2 - 4, random exponents, shared key
+ * and key per row, 9 interleaved repeats; a point counts as faster only where the one launch's slowest repeat is below the
+ * other's fastest; all outputs compared in full first):
+ *   - a step of a blind rotation: tn_poly_cmux_rotate_prepared_dev is faster than the explicit route (tn_monomial_mul_dev,
+ *     tn_poly_external_product_prepared_dev, the addition in torch) at all twelve measured points by disjoint ranges:
+ *     x 0.48 - 0.62 at n = 4096 / 60-bit, 65,536 rows (7,642 against 15,969 us at two terms, shared key; the key per row at four
+ *     terms ran on 32,768 rows) and x 0.54 - 0.66 at n = 1024 / 24-bit, 4,096 rows (72.1 against 134.1 us).  The gain shrinks
+ *     with terms: the saving is a fixed amount per row.
+ *   - against the route's two library launches WITHOUT the addition it is still faster at all twelve points by disjoint ranges,
+ *     x 0.87 - 0.91 at n = 4096 and x 0.93 - 0.97 at n = 1024: a caller with a fused addition of their own gains that much.
+ *   - against a plain tn_poly_external_product_prepared_dev launch on the same rows it is SLOWER at all twelve points, x 1.05 -
+ *     1.14 at n = 4096 (700 - 1,000 us more for 65,536 rows, about the same at every term count) and x 1.08 - 1.14 at n = 1024: that is
+ *     the price of the rotation and the add-in, two more reads of a by count.  How many of them hit in L2 was not isolated.
+ *   - the rotation alone (an automorphism-like gather): tn_monomial_mul_dev; its time is inside the route's figures and was not
+ *     measured by itself.
+ *   - not measured: n = 256, n = 8192, the canonical policy, unsigned digits, a graph of many steps.
+ *
+ * Status of tn_monomial_mul_dev, in this order: TN_EINVAL for a NULL plan; for group == 0; for a flag bit other than
+ * TN_MONOMIAL_MINUS_ONE; for batch * group > 2^31 - 1; batch == 0 succeeds and launches nothing; TN_EINVAL for a NULL buffer
+ * (exps included) and for out's rows overlapping a's (byte ranges): the kernel gathers, nothing runs in place.
+ * Status of tn_poly_cmux_rotate_prepared_dev, in this order: TN_EINVAL for a NULL plan; TN_EUNSUPPORTED for a plan without the
+ * fused kernels; TN_EINVAL for comps == 0 and TN_EUNSUPPORTED for comps other than 2 (the text names the explicit route);
+ * TN_EINVAL for everything the gadget calls refuse (terms == 0, a flag bit other than TN_GADGET_BALANCED, base_log == 0 or
+ * 2^base_log >= q, (terms - 1) * base_log >= 64, batch * comps * comps * terms > 2^31 - 1); batch == 0 succeeds and launches
+ * nothing; TN_EINVAL for a NULL buffer (exps included), for bhat_sets neither 1 nor batch, and for c's batch * comps rows
+ * overlapping a's batch * comps rows or bhat's bhat_sets * comps * comps * terms rows.
+ * Both calls enqueue on the stream and return, and may be stream-captured (a captured launch of the fused call hands rows out
+ * at the fixed stride).  No cyclic variant, no *_host form and no tn_multi_* form.  The reference has no counterpart.
+ */
+#define TN_MONOMIAL_MINUS_ONE 1u
+tn_status tn_monomial_mul_dev(tn_plan *plan, const void *a, const uint32_t *exps, void *out, size_t batch, size_t group,
+                              uint32_t flags, void *stream);
+tn_status tn_poly_cmux_rotate_prepared_dev(tn_plan *plan, const void *a, const uint32_t *exps, const void *bhat, size_t bhat_sets,
+                                           void *c, size_t batch, size_t comps, size_t terms, uint32_t base_log, uint32_t flags,
+                                           void *stream);
+
+/*
  * GALOIS AUTOMORPHISMS: sigma_g : a(x) -> a(x^g) mod (x^n + 1) for odd g, on coefficient rows (tn_automorphism_dev) and on
  * prepared rows (tn_automorphism_prepared_dev).  Every rotation and conjugation of an RLWE scheme applies one before its key
  * switch (tn_poly_gadget_multidot_prepared_dev); traces, ring packing and hoisted rotations apply them to prepared rows.

@@ -70,6 +70,14 @@ struct __attribute__((visibility("hidden"))) ApiCheck {          // (hidden, sta
     return !(ins_ >= 2 && outs_ == 1) ||
            fail(TN_EUNSUPPORTED, "2 or more input polynomials into 1 output component are not supported (tn_gadget_decompose_dev, then tn_poly_dot_prepared_dev)");
   }
+  // components of the accumulator of tn_poly_cmux_rotate_prepared_dev: the kernel has two output components
+  bool comps(size_t comps_) {
+    if (!comps_) return fail(TN_EINVAL, "comps must be 2");
+    return comps_ == 2 || fail(TN_EUNSUPPORTED, "comps other than 2 is not supported (tn_monomial_mul_dev, tn_poly_external_product_prepared_dev, then an addition)");
+  }
+  // rows per batch item and flags of tn_monomial_mul_dev
+  bool group(size_t group_) { return group_ || fail(TN_EINVAL, "group must be at least 1"); }
+  bool monomial_flags(uint32_t flags) { return !(flags & ~(uint32_t)TN_MONOMIAL_MINUS_ONE) || fail(TN_EINVAL, "unknown flag bit"); }
   // Galois elements of the automorphism calls: 1 .. TN_GALOIS_MAX of them, each odd and below 2n.  A NULL list is the
   // buffer check's to refuse (behind batch == 0).
   bool galois(const uint32_t* g, size_t count) {
@@ -157,6 +165,21 @@ static inline bool check_external_product(ApiCheck& k, const void* a, const void
          k.gadget(rows_times(rows_times(batch, outs), ins), terms, base_log, flags, "batch * outs * ins * terms") && k.work(batch) &&
          k.buffers(a && bhat && c) && k.sets(sets, batch, "bhat_sets", "one set of operands for every row") &&
          k.apart(c, batch * outs, a, batch * ins, "an input") && k.apart(c, batch * outs, bhat, sets * outs * ins * terms, "an input");
+}
+// tn_monomial_mul_dev: out has the batch * group rows of a; exps is a device array that the host never reads.  The kernel
+// gathers, so nothing runs in place.
+static inline bool check_monomial(ApiCheck& k, const void* a, const void* exps, const void* out, size_t batch, size_t group, uint32_t flags) {
+  return k.plan() && k.group(group) && k.monomial_flags(flags) && k.rows(batch, group, "batch * group", "rows") && k.work(batch) &&
+         k.buffers(a && exps && out) && k.apart(out, batch * group, a, batch * group, "the input");
+}
+// tn_poly_cmux_rotate_prepared_dev: check_external_product's list with ins = outs = comps and exps among the buffers: the row
+// limit holds for batch * comps * comps * terms, a and c have batch * comps rows and bhat sets * comps * comps * terms
+static inline bool check_cmux_rotate(ApiCheck& k, const void* a, const void* exps, const void* bhat, size_t sets, const void* c, size_t batch,
+                                     size_t comps, size_t terms, uint32_t base_log, uint32_t flags) {
+  return k.plan() && k.fused() && k.comps(comps) &&
+         k.gadget(rows_times(rows_times(batch, comps), comps), terms, base_log, flags, "batch * comps * comps * terms") && k.work(batch) &&
+         k.buffers(a && exps && bhat && c) && k.sets(sets, batch, "bhat_sets", "one set of operands for every row") &&
+         k.apart(c, batch * comps, a, batch * comps, "an input") && k.apart(c, batch * comps, bhat, sets * comps * comps * terms, "an input");
 }
 // tn_automorphism_dev and, with the fused() step (prepared), tn_automorphism_prepared_dev: out has batch * count rows.  The
 // kernels gather, so nothing runs in place.

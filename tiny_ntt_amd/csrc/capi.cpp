@@ -292,6 +292,23 @@ extern "C" tn_status tn_poly_external_product_prepared_dev(tn_plan* p, const voi
   return TN_OK;
 }
 
+// ---- CMux rotation step: the monomial product with an exponent per item, read on the device; the fused step -----------
+extern "C" tn_status tn_monomial_mul_dev(tn_plan* p, const void* a, const uint32_t* exps, void* out, size_t batch, size_t group, uint32_t flags,
+                                         void* stream) {
+  TN_CHECK("tn_monomial_mul_dev", check_monomial(k, a, exps, out, batch, group, flags));
+  TN_ON_DEVICE(p);
+  TN_HIP(launch_monomial_mul(p, a, exps, out, batch, group, (flags & TN_MONOMIAL_MINUS_ONE) != 0, pick_stream(p, stream)));
+  return TN_OK;
+}
+
+extern "C" tn_status tn_poly_cmux_rotate_prepared_dev(tn_plan* p, const void* a, const uint32_t* exps, const void* bhat, size_t bhat_sets, void* c,
+                                                      size_t batch, size_t comps, size_t terms, uint32_t base_log, uint32_t flags, void* stream) {
+  TN_CHECK("tn_poly_cmux_rotate_prepared_dev", check_cmux_rotate(k, a, exps, bhat, bhat_sets, c, batch, comps, terms, base_log, flags));
+  TN_ON_DEVICE(p);
+  TN_HIP(launch_polydot_cmux(p, a, exps, bhat, bhat_sets == 1, c, batch, terms, base_log, (flags & TN_GADGET_BALANCED) != 0, pick_stream(p, stream)));
+  return TN_OK;
+}
+
 // ---- ring automorphisms a(x) -> a(x^g): count images of every row, the elements by value in the kernel arguments -----------
 extern "C" tn_status tn_automorphism_dev(tn_plan* p, const void* a, void* out, size_t batch, const uint32_t* galois, size_t count, void* stream) {
   TN_CHECK("tn_automorphism_dev", check_automorphism(k, a, out, batch, galois, count, false));

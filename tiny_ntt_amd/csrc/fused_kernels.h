@@ -7,6 +7,7 @@
 //   kernels_hat.hip       transform domain: both operands prepared; unprepare
 //   kernels_gadget.hip    gadget decomposition and the dot product that decomposes a itself
 //   kernels_extprod.hip   external product: the digits of all input polynomials of a row into both output components
+//   kernels_cmux.hip      CMux rotation step: the external product of (X^e - 1) * a, added to a
 #pragma once
 #include <hip/hip_runtime.h>
 #include <type_traits>

@@ -175,7 +175,7 @@ inline hipError_t launch_persistent(const tn_plan* p, hipStream_t s, const void*
 }
 
 // kernels.hip (prepared operand: kernels_prepared.hip; transform domain: kernels_hat.hip; gadget: kernels_gadget.hip;
-// automorphisms: kernels_galois.hip; external product: kernels_extprod.hip)
+// automorphisms: kernels_galois.hip; external product: kernels_extprod.hip; CMux rotation step: kernels_cmux.hip)
 bool fused_supported(u32 logn, int elem_bytes);
 const char* fused_kernel_name(const tn_plan* p);
 const char* cg_kernel_name(const tn_plan* p, int group, int layout);
@@ -205,6 +205,12 @@ hipError_t launch_polydot_gadget2(const tn_plan* p, const void* a, const void* b
 // input polynomials of a row into both components, c[r][o] = sum_i sum_j digit_j(a[r][i]) * b[shared ? 0 : r][o][i][j], o < 2
 hipError_t launch_polydot_extprod(const tn_plan* p, const void* a, const void* bhat, bool shared, void* c, size_t batch, size_t ins, size_t terms,
                                   tn::u32 base_log, bool balanced, hipStream_t s);
+// CMux rotation step (kernels_cmux.hip).  tn_monomial_mul_dev, every plan: out[item][g] = X^e * a[item][g], or (X^e - 1) * with
+// minus_one, e = exps[item] & (2n - 1) read on the device, g < group.  tn_poly_cmux_rotate_prepared_dev, fused plans only:
+// c[r][o] = a[r][o] + sum_{i < 2} sum_j digit_j((X^e_r - 1) * a[r][i]) * b[shared ? 0 : r][o][i][j], o < 2
+hipError_t launch_monomial_mul(const tn_plan* p, const void* a, const uint32_t* exps, void* out, size_t batch, size_t group, bool minus_one, hipStream_t s);
+hipError_t launch_polydot_cmux(const tn_plan* p, const void* a, const uint32_t* exps, const void* bhat, bool shared, void* c, size_t batch, size_t terms,
+                               tn::u32 base_log, bool balanced, hipStream_t s);
 // ring automorphisms a(x) -> a(x^g) (kernels_galois.hip): count images of every row, out[r][m] = sigma_{galois[m]}(row r); on
 // coefficient rows (tn_automorphism_dev: every plan) and on prepared rows (tn_automorphism_prepared_dev: fused plans only)
 hipError_t launch_automorphism(const tn_plan* p, const void* a, void* out, size_t batch, const uint32_t* galois, size_t count, hipStream_t s);

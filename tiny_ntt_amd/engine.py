@@ -32,6 +32,7 @@ VARIANTS = {"auto": VARIANT_AUTO, "fused": VARIANT_FUSED, "cg": VARIANT_CG, "cg8
 CG_VARIANTS = tuple(k for k in VARIANTS if k.startswith("cg"))
 PLAN_FORCE_CANONICAL = 1
 GALOIS_MAX = 16               # Galois elements per automorphism call: include/tinyntt.h TN_GALOIS_MAX
+MONOMIAL_MINUS_ONE = 1        # (X^e - 1) * a instead of X^e * a: include/tinyntt.h TN_MONOMIAL_MINUS_ONE
 GADGET_BALANCED = 1           # digits in [-B/2, B/2): include/tinyntt.h TN_GADGET_BALANCED
 PLAN_CANONICAL_INPUTS = 2     # the caller promises inputs in [0, q): include/tinyntt.h TN_PLAN_CANONICAL_INPUTS
 
@@ -43,6 +44,7 @@ EXPORTED_SYMBOLS = (
     "tn_prepare_dev", "tn_poly_mult_prepared_dev", "tn_poly_dot_prepared_dev", "tn_unprepare_dev", "tn_poly_dot_hat_dev",
     "tn_gadget_decompose_dev", "tn_poly_gadget_dot_prepared_dev", "tn_poly_gadget_multidot_prepared_dev",
     "tn_poly_external_product_prepared_dev",
+    "tn_monomial_mul_dev", "tn_poly_cmux_rotate_prepared_dev",
     "tn_automorphism_dev", "tn_automorphism_prepared_dev",
     "tn_plan_export_table", "tn_ntt_forward_dev", "tn_ntt_inverse_dev",
     "tn_ntt_forward_host", "tn_ntt_inverse_host", "tn_ntt_forward_trace_host", "tn_twisted_ntt_forward_dev",
@@ -105,6 +107,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.tn_poly_gadget_dot_prepared_dev.argtypes = [vp, vp, vp, sz, vp, sz, sz, u32, u32, vp]
     lib.tn_poly_gadget_multidot_prepared_dev.argtypes = [vp, vp, vp, sz, vp, sz, sz, sz, u32, u32, vp]
     lib.tn_poly_external_product_prepared_dev.argtypes = [vp, vp, vp, sz, vp, sz, sz, sz, sz, u32, u32, vp]
+    lib.tn_monomial_mul_dev.argtypes = [vp, vp, vp, vp, sz, sz, u32, vp]
+    lib.tn_poly_cmux_rotate_prepared_dev.argtypes = [vp, vp, vp, vp, sz, vp, sz, sz, sz, u32, u32, vp]
     lib.tn_automorphism_dev.argtypes = [vp, vp, vp, sz, ctypes.POINTER(u32), sz, vp]
     lib.tn_automorphism_prepared_dev.argtypes = [vp, vp, vp, sz, ctypes.POINTER(u32), sz, vp]
     lib.tn_schoolbook_dev.argtypes = [vp, vp, vp, vp, sz, vp]
@@ -531,6 +535,116 @@ class Plan:
                                                                           ins, outs, terms, int(base_log), GADGET_BALANCED if balanced else 0,
                                                                           self._stream_ptr(stream)))
         return self._result(c.reshape(batch, outs, self.n) if host else c, host, one, out)
+
+    # ---- the CMux rotation step of a blind rotation ----------------------------------
+    def _exps(self, exps, batch, device):
+        """exps, a device tensor or host integers of `batch` entries -> a contiguous device tensor of 32-bit words (values are
+        taken mod 2n by the kernels; host values are reduced here so that any Python integer fits the word)."""
+        import torch
+        if _is_torch(exps):
+            if not exps.is_cuda:
+                raise TinyNttError(TN_EINVAL, "exps: torch tensor must live on a HIP device")
+            if exps.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or not exps.is_contiguous():
+                raise TinyNttError(TN_EINVAL, "exps: need a contiguous tensor of 32-bit integers")
+            if exps.numel() != batch:
+                raise ValueError(f"Expected {batch} exponents, got {exps.numel()}")
+            return exps
+        h = np.asarray(exps)
+        if h.dtype == object or h.dtype.kind in "iu":
+            h = np.array([int(v) % (2 * self.n) for v in h.ravel()], dtype=np.int64)
+        else:
+            raise TypeError(f"exps: exponents must be integers, got dtype {h.dtype}")
+        if h.size != batch:
+            raise ValueError(f"Expected {batch} exponents, got {h.size}")
+        return torch.from_numpy(h.astype(np.int32)).to(device)
+
+    def monomial_mul(self, a, exps, minus_one=False, out=None, stream=None):
+        """X^e * a (or, with minus_one, (X^e - 1) * a) in Z_q[x]/(x^n + 1) with an exponent per batch item, any integer taken mod 2n
+        (tn_monomial_mul_dev; include/tinyntt.h has the definition).  a is (batch, n) or (batch, group, n): exponent exps[r]
+        applies to all `group` rows of item r; host values or a device tensor.  exps: a device tensor of 32-bit integers or host
+        integers, `batch` entries.  Returns canonical residues in the shape of a; host arrays in give host arrays out.  Works
+        on every plan."""
+        import torch
+        host = not _is_torch(a)
+        if host:
+            a = np.asarray(a)
+        if a.ndim not in (2, 3) or a.shape[-1] != self.n or (a.ndim == 3 and a.shape[1] == 0):
+            raise ValueError(f"Expected a of shape (batch, {self.n}) or (batch, group, {self.n})")
+        shape = tuple(int(v) for v in a.shape)
+        batch, group = shape[0], (shape[1] if len(shape) == 3 else 1)
+        if host:
+            a = self.to_device(a.reshape(batch * group, self.n))
+        else:
+            if not a.is_contiguous():
+                raise TinyNttError(TN_EINVAL, f"a: need a contiguous tensor of {self.elem_bytes}-byte integers")
+            self._dev_rows(a.reshape(batch * group, self.n), "a")
+        e = self._exps(exps, batch, a.device)
+        c = out if out is not None else torch.empty((batch * group, self.n), dtype=self.torch_dtype, device=a.device)
+        if not _is_torch(c) or c.numel() != batch * group * self.n or not c.is_contiguous():
+            raise ValueError(f"Expected an output of {batch} x {group} rows of {self.n} coefficients")
+        self._dev_rows(c.reshape(batch * group, self.n), "out")
+        _check(self._lib, self._lib.tn_monomial_mul_dev(self._h, a.data_ptr(), e.data_ptr(), c.data_ptr(), batch, group,
+                                                        MONOMIAL_MINUS_ONE if minus_one else 0, self._stream_ptr(stream)))
+        if host:
+            return self.to_host(c).reshape(shape)
+        return c if out is not None else c.reshape(shape)
+
+    def poly_cmux_rotate_prepared(self, a, exps, prepared: PreparedOperand, terms, base_log, balanced=False, out=None, stream=None):
+        """One step of a blind rotation from ONE launch (tn_poly_cmux_rotate_prepared_dev):
+        c[r] = a[r] + RGSW [x] ((X^e_r - 1) * a[r]), that is c[r][o] = a[r][o] + sum_i sum_j digit_j((X^e_r - 1) a[r][i]) * b[r][o][i][j].
+        a is (batch, 2, n), or (2, n) for one ciphertext, host values or a device tensor; exps as in monomial_mul; the prepared
+        operand has batch * 4 * terms rows ([batch][2][2][terms]), or 4 * terms rows that every row is multiplied by.  Returns
+        (batch, 2, n) or (2, n), bit-identical to monomial_mul(minus_one=True), poly_external_product_prepared and the addition
+        mod q.  out must not be a: a blind rotation alternates two buffers (Plan.blind_rotate)."""
+        import torch
+        self._own_prepared(prepared, "poly_cmux_rotate_prepared", "key")
+        host = not _is_torch(a)
+        if host:
+            a = np.asarray(a)
+        if a.ndim not in (2, 3) or a.shape[-1] != self.n or a.shape[-2] == 0:
+            raise ValueError(f"Expected a of shape (batch, comps, {self.n}) or (comps, {self.n})")
+        one = a.ndim == 2
+        comps = int(a.shape[-2])
+        batch = 1 if one else int(a.shape[0])
+        if host:
+            a = self.to_device(a.reshape(batch * comps, self.n))
+        else:
+            if not a.is_contiguous():
+                raise TinyNttError(TN_EINVAL, f"a: need a contiguous tensor of {self.elem_bytes}-byte integers")
+            self._dev_rows(a.reshape(batch * comps, self.n), "a")
+        terms = int(terms)
+        if terms < 1:
+            raise ValueError(f"Expected terms >= 1, got {terms}")
+        sets = self._sets(prepared, batch, comps * comps * terms, "key")
+        e = self._exps(exps, batch, a.device)
+        c = out if out is not None else torch.empty((batch, comps, self.n), dtype=self.torch_dtype, device=a.device)
+        if not _is_torch(c) or c.numel() != batch * comps * self.n or not c.is_contiguous():
+            raise ValueError(f"Expected an output of {batch} x {comps} rows of {self.n} coefficients")
+        self._dev_rows(c.reshape(batch * comps, self.n), "out")        # on the device, the plan's words: poly_gadget_dot_prepared's check
+        _check(self._lib, self._lib.tn_poly_cmux_rotate_prepared_dev(self._h, a.data_ptr(), e.data_ptr(), prepared.tensor.data_ptr(), sets,
+                                                                     c.data_ptr(), batch, comps, terms, int(base_log),
+                                                                     GADGET_BALANCED if balanced else 0, self._stream_ptr(stream)))
+        return self._result(c.reshape(batch, comps, self.n) if host else c, host, one, out)
+
+    def blind_rotate(self, acc, exps, prepared: PreparedOperand, terms, base_log, balanced=False, stream=None):
+        """acc <- acc + RGSW_k [x] ((X^exps[k][r] - 1) * acc) for k = 0 .. steps - 1: poly_cmux_rotate_prepared step by step over two
+        alternating buffers.  acc is a device tensor (batch, 2, n), left as it is; exps is (steps, batch), a device tensor of
+        32-bit integers or host integers; prepared holds steps * 4 * terms rows, one shared key per step.  Returns the last
+        buffer written (acc itself for no step)."""
+        import torch
+        self._own_prepared(prepared, "blind_rotate", "key")
+        if not _is_torch(acc) or acc.dim() != 3:
+            raise ValueError(f"Expected acc as a device tensor of shape (batch, 2, {self.n})")
+        batch, steps, key = int(acc.shape[0]), len(exps), 4 * int(terms)
+        if prepared.rows != steps * key:
+            raise ValueError(f"Expected a key of {steps} x {key} rows, got {prepared.rows}")
+        if not _is_torch(exps):
+            exps = self._exps(np.asarray(exps).reshape(-1), steps * batch, acc.device).reshape(steps, batch)
+        bufs = [torch.empty_like(acc), torch.empty_like(acc)]
+        for k in range(steps):
+            step_key = PreparedOperand(self, prepared.tensor[k * key:(k + 1) * key], key)
+            acc = self.poly_cmux_rotate_prepared(acc, exps[k], step_key, terms, base_log, balanced, out=bufs[k & 1], stream=stream)
+        return acc
 
     # ---- ring automorphisms a(x) -> a(x^g) ----------------------------------------
     @staticmethod
