@@ -428,6 +428,56 @@ tn_status tn_poly_cmux_rotate_prepared_dev(tn_plan *plan, const void *a, const u
                                            void *stream);
 
 /*
+ * BLIND ROTATION FROM ONE LAUNCH: `steps` CMux rotation steps per ciphertext with the accumulator kept in LDS across them
+ * (tn_poly_blind_rotate_prepared_dev).  A row's blind rotation depends on no other row, so the workgroup that takes a row keeps
+ * it for all steps: a is read once, c is written once, the rotated words and the add-in words of every step come from LDS, and
+ * the only global traffic of a step is its key (shared by every row: L2) and one scalar load of the exponent.  One launch
+ * instead of `steps`, no launch boundary between steps.
+ *
+ * a and c are [batch][2][n].  exps is a DEVICE array [steps][batch] (the layout of Plan.blind_rotate); any word is taken mod 2n
+ * and the index is masked to the row, as above: no content of exps can cause an out-of-bounds access, and a captured launch sees
+ * the exponents that are in the buffer at replay time.  bhat is [steps][2][2][terms][n] prepared rows: ONE KEY PER STEP, shared by
+ * every row (a key per row and step is out of scope).  comps must be 2.  Digits, base_log and flags are the gadget calls'.
+ * The result is BIT-IDENTICAL to `steps` calls of tn_poly_cmux_rotate_prepared_dev with bhat_sets = 1, step k on key k
+ * (bhat + k * 4 * terms rows) and exps + k * batch.
+ * c == a, the same pointer, is allowed (in place): a workgroup reads its row before it writes it and no other workgroup touches
+ * that row.  Any other overlap of c with a, and any overlap of c with bhat, is refused.
+ *
+ * Shapes.  A fused plan is supported when the kernel's LDS request (the CMux step's layout plus two rows of n words) fits the
+ * 160 KiB of one workgroup (csrc/launch_plan.h: blindrot_supported; tests/test_blindrot_emu.py walks every shape).  Supported:
+ * n = 256 .. 4096 with 32-bit and with 64-bit words, n = 8192 with 32-bit words.  Over the limit: n = 8192 with 64-bit words
+ * alone (two rows are 128 KiB beside a transpose image of 64 KiB and more): TN_EUNSUPPORTED, and the text names the loop over
+ * tn_poly_cmux_rotate_prepared_dev.
+ *
+ * When to use which (MI355X, profiles/blindrot_ab.txt, tools/gpu_blindrot.py; balanced digits, random exponents, terms 2 and 3,
+ * 9 interleaved repeats, the output compared in full with the loop's first; a point counts as faster only where the one launch's
+ * slowest repeat is below the other's fastest):
+ *   - a few hundred ciphertexts (batch 256: fewer rows than workgroups can be resident): the one launch is FASTER than the loop
+ *     of tn_poly_cmux_rotate_prepared_dev launches at all six points by disjoint ranges, x 0.77 - 0.86 (n = 4096 / 60-bit, 16
+ *     steps, two terms: 577 against 746 us; n = 1024 / 24-bit, 64 steps: 840 against 1,051 us), and as much faster than the same
+ *     launches replayed from one captured graph (x 0.77 - 0.85): the graph does not remove the per-launch cost, the one launch does.
+ *   - thousands of ciphertexts (batch 4,096): the one launch is SLOWER than the loop at all six points by disjoint ranges,
+ *     x 1.04 - 1.08 at n = 1024 / 24-bit, x 1.06 - 1.10 at n = 2048 / 60-bit, x 1.13 - 1.16 at n = 4096 / 60-bit (9,073 against
+ *     8,046 us at two terms), and slower than the graph (x 1.03 - 1.11).  The launch cost is small beside a step there, and the
+ *     accumulator's LDS leaves fewer resident workgroups per CU than the step kernel has.  Use the loop (Plan.blind_rotate), or
+ *     split the batch.
+ *   - where the crossover lies between 256 and 4,096 rows was not measured; nor were n = 256, 512, 8192, the canonical policy,
+ *     unsigned digits, step counts other than 64 (n = 1024) and 16, and in-place launches.
+ *
+ * Status, in this order: TN_EINVAL for a NULL plan; TN_EUNSUPPORTED for a plan without the fused kernels and for a shape over
+ * the LDS limit; TN_EINVAL for comps == 0 and TN_EUNSUPPORTED for comps other than 2; TN_EINVAL for steps == 0; for everything
+ * the gadget calls refuse (terms == 0, a flag bit other than TN_GADGET_BALANCED, base_log == 0 or 2^base_log >= q,
+ * (terms - 1) * base_log >= 64); for steps * 4 * terms, batch * 2 or steps * batch above 2^31 - 1 (a text each); batch == 0
+ * succeeds and launches nothing; TN_EINVAL for a NULL buffer (exps included), for c overlapping a without being a, and for c
+ * overlapping bhat's steps * 4 * terms rows (byte ranges).
+ * The call enqueues on the stream and returns, and may be stream-captured (a captured launch hands rows out at the fixed
+ * stride).  No cyclic variant, no *_host form and no tn_multi_* form.  The reference has no counterpart.
+ */
+tn_status tn_poly_blind_rotate_prepared_dev(tn_plan *plan, const void *a, const uint32_t *exps, const void *bhat, void *c,
+                                            size_t batch, size_t comps, size_t steps, size_t terms, uint32_t base_log,
+                                            uint32_t flags, void *stream);
+
+/*
  * GALOIS AUTOMORPHISMS: sigma_g : a(x) -> a(x^g) mod (x^n + 1) for odd g, on coefficient rows (tn_automorphism_dev) and on
  * prepared rows (tn_automorphism_prepared_dev).  Every rotation and conjugation of an RLWE scheme applies one before its key
  * switch (tn_poly_gadget_multidot_prepared_dev); traces, ring packing and hoisted rotations apply them to prepared rows.

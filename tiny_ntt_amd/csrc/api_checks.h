@@ -7,10 +7,12 @@
 #include <stdint.h>
 #include <string>
 #include "../../include/tinyntt.h"
+#include "launch_plan.h"
 
 namespace tn {
 
-struct ApiPlan { uint32_t n; int elem_bytes; bool has_fused, omega_only; uint64_t q; };     // a NULL plan: n == 0
+// (lazy: the plan's policy, which names its fused shape together with n and elem_bytes; only check_blind_rotate asks)
+struct ApiPlan { uint32_t n; int elem_bytes; bool has_fused, omega_only; uint64_t q; bool lazy = false; };     // a NULL plan: n == 0
 
 struct KernelPick { bool known, fused; int group, layout; };     // layout: CgLayout, cg_core.h (0 linear, 1 padded, 2 swizzled)
 // The kernel a variant names; TN_VARIANT_AUTO is the fused kernel where the plan has it (and no trace is wanted), else CG.
@@ -51,12 +53,12 @@ struct __attribute__((visibility("hidden"))) ApiCheck {          // (hidden, sta
   }
   bool out_prepared(int flag) { return flag == 0 || flag == 1 || fail(TN_EINVAL, "out_prepared must be 0 (coefficients) or 1 (prepared rows)"); }
   // what both gadget calls ask: terms >= 1, known flags, 0 < base_log, 2^base_log < q, no shift reaches the word width
-  bool gadget(size_t batch, size_t terms_, uint32_t base_log, uint32_t flags, const char* count = "batch * terms") {
+  bool gadget(size_t batch, size_t terms_, uint32_t base_log, uint32_t flags, const char* count = "batch * terms", const char* noun = "digit rows") {
     if (!terms(terms_)) return false;
     if (flags & ~(uint32_t)TN_GADGET_BALANCED) return fail(TN_EINVAL, "unknown flag bit");
     if (base_log == 0 || base_log >= 64 || (((uint64_t)1) << base_log) >= v.q) return fail(TN_EINVAL, "need 1 <= base_log and 2^base_log < q");
     if (terms_ - 1 > 63 / base_log) return fail(TN_EINVAL, "(terms - 1) * base_log must be below 64");
-    return rows(batch, terms_, count, "digit rows");
+    return rows(batch, terms_, count, noun);
   }
   // output components of tn_poly_gadget_multidot_prepared_dev: one runs the gadget kernel, two the kernel built for them
   bool outs(size_t outs_) {
@@ -74,6 +76,19 @@ struct __attribute__((visibility("hidden"))) ApiCheck {          // (hidden, sta
   bool comps(size_t comps_) {
     if (!comps_) return fail(TN_EINVAL, "comps must be 2");
     return comps_ == 2 || fail(TN_EUNSUPPORTED, "comps other than 2 is not supported (tn_monomial_mul_dev, tn_poly_external_product_prepared_dev, then an addition)");
+  }
+  // tn_poly_blind_rotate_prepared_dev: the steps; the shape, whose LDS request must fit a workgroup (launch_plan.h:
+  // blindrot_supported); and c == a, the same pointer, as the one overlap of the two that is allowed
+  bool steps(size_t steps_) { return steps_ || fail(TN_EINVAL, "steps must be at least 1"); }
+  bool blindrot_shape() {
+    uint32_t logn = 0;
+    while ((1ull << logn) < v.n) ++logn;
+    return blindrot_supported(v.elem_bytes, v.lazy, logn) ||
+           fail(TN_EUNSUPPORTED, "the accumulator of this shape does not fit a workgroup's LDS (loop over tn_poly_cmux_rotate_prepared_dev)");
+  }
+  bool apart_or_same(const void* out, const void* in, size_t rows_) {
+    const uintptr_t o = (uintptr_t)out, i = (uintptr_t)in, bytes = rows_ * (uintptr_t)v.n * (uintptr_t)v.elem_bytes;
+    return o == i || !(o < i + bytes && i < o + bytes) || fail(TN_EINVAL, "c may be a itself (in place) but must not overlap it otherwise");
   }
   // rows per batch item and flags of tn_monomial_mul_dev
   bool group(size_t group_) { return group_ || fail(TN_EINVAL, "group must be at least 1"); }
@@ -180,6 +195,15 @@ static inline bool check_cmux_rotate(ApiCheck& k, const void* a, const void* exp
          k.gadget(rows_times(rows_times(batch, comps), comps), terms, base_log, flags, "batch * comps * comps * terms") && k.work(batch) &&
          k.buffers(a && exps && bhat && c) && k.sets(sets, batch, "bhat_sets", "one set of operands for every row") &&
          k.apart(c, batch * comps, a, batch * comps, "an input") && k.apart(c, batch * comps, bhat, sets * comps * comps * terms, "an input");
+}
+// tn_poly_blind_rotate_prepared_dev: check_cmux_rotate's order with the steps behind the components.  One key per step, shared
+// by every row: bhat has steps * 4 * terms rows, exps steps * batch words, a and c batch * 2 rows; c may be a itself.
+static inline bool check_blind_rotate(ApiCheck& k, const void* a, const void* exps, const void* bhat, const void* c, size_t batch, size_t comps,
+                                      size_t steps, size_t terms, uint32_t base_log, uint32_t flags) {
+  return k.plan() && k.fused() && k.blindrot_shape() && k.comps(comps) && k.steps(steps) &&
+         k.gadget(rows_times(steps, 4), terms, base_log, flags, "steps * 4 * terms", "key rows") &&
+         k.rows(batch, 2, "batch * 2", "accumulator rows") && k.rows(steps, batch, "steps * batch", "exponents") && k.work(batch) &&
+         k.buffers(a && exps && bhat && c) && k.apart_or_same(c, a, batch * 2) && k.apart(c, batch * 2, bhat, steps * 4 * terms, "the key");
 }
 // tn_automorphism_dev and, with the fused() step (prepared), tn_automorphism_prepared_dev: out has batch * count rows.  The
 // kernels gather, so nothing runs in place.

@@ -181,7 +181,7 @@ extern "C" int tn_plan_is_general(const tn_plan* p) { return p && p->general && 
 static hipStream_t pick_stream(tn_plan* p, void* stream) { return stream ? (hipStream_t)stream : p->stream; }
 
 // ---- the device entry points: the argument checks (api_checks.h: an ordered list of steps per entry point), then the launch ----
-static ApiPlan view(const tn_plan* p) { return p ? ApiPlan{p->n, p->elem_bytes, p->has_fused, p->omega_only, p->q} : ApiPlan{}; }
+static ApiPlan view(const tn_plan* p) { return p ? ApiPlan{p->n, p->elem_bytes, p->has_fused, p->omega_only, p->q, p->lazy} : ApiPlan{}; }
 static tn_status refused(const ApiCheck& k) {          // the answer of a list that stopped; TN_OK when there was nothing to do
   if (k.st) g_err = k.msg;
   return k.st;
@@ -306,6 +306,15 @@ extern "C" tn_status tn_poly_cmux_rotate_prepared_dev(tn_plan* p, const void* a,
   TN_CHECK("tn_poly_cmux_rotate_prepared_dev", check_cmux_rotate(k, a, exps, bhat, bhat_sets, c, batch, comps, terms, base_log, flags));
   TN_ON_DEVICE(p);
   TN_HIP(launch_polydot_cmux(p, a, exps, bhat, bhat_sets == 1, c, batch, terms, base_log, (flags & TN_GADGET_BALANCED) != 0, pick_stream(p, stream)));
+  return TN_OK;
+}
+
+// ---- blind rotation: `steps` CMux rotation steps from one launch, the accumulator in LDS across them ------------------------
+extern "C" tn_status tn_poly_blind_rotate_prepared_dev(tn_plan* p, const void* a, const uint32_t* exps, const void* bhat, void* c, size_t batch,
+                                                       size_t comps, size_t steps, size_t terms, uint32_t base_log, uint32_t flags, void* stream) {
+  TN_CHECK("tn_poly_blind_rotate_prepared_dev", check_blind_rotate(k, a, exps, bhat, c, batch, comps, steps, terms, base_log, flags));
+  TN_ON_DEVICE(p);
+  TN_HIP(launch_polydot_blindrot(p, a, exps, bhat, c, batch, steps, terms, base_log, (flags & TN_GADGET_BALANCED) != 0, pick_stream(p, stream)));
   return TN_OK;
 }
 

@@ -125,4 +125,39 @@ inline RowPlan plan_rows(size_t row_bytes, size_t batch, size_t resident, const 
 // rows are planned with: a chunk stays at or above chunk_bytes of operand per atomic however short a single row is.
 inline size_t dot_row_bytes(size_t operand_row_bytes, size_t terms) { return operand_row_bytes * terms; }
 
+// Blind rotation in one launch (polydot_blindrot_kernel, kernels_blindrot.hip): the LDS request of a workgroup is the CMux
+// step's layout (the transpose image, xl * THREADS words of an input put away, two staged twiddle tables, the next-row slot:
+// fused_lds_bytes of fused_kernels.h) plus the accumulator, two rows of n words.  A shape is supported when that request fits
+// the 160 KiB a workgroup can have.  One rule for the launcher, the argument check (api_checks.h) and the CPU stepping.
+constexpr size_t BLINDROT_WG_LDS = 160 * 1024;
+constexpr size_t BLINDROT_WAVES = 4;                 // waves per SIMD the kernel is built for (dot_waves, fused_kernels.h)
+template <typename Sh> constexpr size_t blindrot_lds_bytes(int xl) {
+  typedef typename Sh::Cfg Cfg;
+  return ((size_t)Cfg::lds_elems() + (size_t)xl * Cfg::THREADS + 2 * (size_t)Cfg::N) * sizeof(typename Sh::E) +
+         2 * (size_t)Cfg::lds_tw_count() * sizeof(typename TwOf<typename Sh::E>::type) + 16;
+}
+// Words of an input polynomial per thread put away in LDS instead of registers: as many as leave the CU the resident
+// workgroups it has with none put away (what LDS holds, what the waves allow, one at least), chosen from the resource report
+// (DESIGN.md 3.2i).
+template <typename Sh> constexpr int blindrot_lds_words() {
+  typedef typename Sh::Cfg Cfg;
+  const size_t base = blindrot_lds_bytes<Sh>(0), word_row = (size_t)Cfg::THREADS * sizeof(typename Sh::E);
+  const size_t waves = (size_t)(Cfg::THREADS + 63) / 64, by_waves = 4 * BLINDROT_WAVES / waves;
+  size_t wgs = BLINDROT_WG_LDS / base;
+  if (wgs > by_waves) wgs = by_waves;
+  if (wgs < 1) wgs = 1;
+  int x = Cfg::R;
+  while (x > 0 && BLINDROT_WG_LDS / (base + (size_t)x * word_row) < wgs) --x;
+  // 64-bit words: half of them at least.  With fewer put away the n = 512 kernels use scratch (12 - 80 bytes per lane with 0
+  // and 2 of 8; none with 4), and no instantiation may; the rule by itself gives 0 only there.
+  if (sizeof(typename Sh::E) == 8 && x < Cfg::R / 2) x = Cfg::R / 2;
+  return x;
+}
+template <typename Sh> constexpr bool blindrot_lds_fits() { return blindrot_lds_bytes<Sh>(blindrot_lds_words<Sh>()) <= BLINDROT_WG_LDS; }
+// ... of a plan's (elem_bytes, lazy, logn); false where no fused kernel is built for that n.  Over the limit: n = 8192 with
+// 64-bit words alone (tests/test_blindrot_emu.py walks the list).
+inline bool blindrot_supported(int elem_bytes, bool lazy, u32 logn) {
+  return with_fused_shape(elem_bytes, lazy, logn, false, [](auto sh) { return blindrot_lds_fits<decltype(sh)>(); });
+}
+
 }  // namespace tn

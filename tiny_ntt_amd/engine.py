@@ -44,7 +44,7 @@ EXPORTED_SYMBOLS = (
     "tn_prepare_dev", "tn_poly_mult_prepared_dev", "tn_poly_dot_prepared_dev", "tn_unprepare_dev", "tn_poly_dot_hat_dev",
     "tn_gadget_decompose_dev", "tn_poly_gadget_dot_prepared_dev", "tn_poly_gadget_multidot_prepared_dev",
     "tn_poly_external_product_prepared_dev",
-    "tn_monomial_mul_dev", "tn_poly_cmux_rotate_prepared_dev",
+    "tn_monomial_mul_dev", "tn_poly_cmux_rotate_prepared_dev", "tn_poly_blind_rotate_prepared_dev",
     "tn_automorphism_dev", "tn_automorphism_prepared_dev",
     "tn_plan_export_table", "tn_ntt_forward_dev", "tn_ntt_inverse_dev",
     "tn_ntt_forward_host", "tn_ntt_inverse_host", "tn_ntt_forward_trace_host", "tn_twisted_ntt_forward_dev",
@@ -109,6 +109,7 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.tn_poly_external_product_prepared_dev.argtypes = [vp, vp, vp, sz, vp, sz, sz, sz, sz, u32, u32, vp]
     lib.tn_monomial_mul_dev.argtypes = [vp, vp, vp, vp, sz, sz, u32, vp]
     lib.tn_poly_cmux_rotate_prepared_dev.argtypes = [vp, vp, vp, vp, sz, vp, sz, sz, sz, u32, u32, vp]
+    lib.tn_poly_blind_rotate_prepared_dev.argtypes = [vp, vp, vp, vp, vp, sz, sz, sz, sz, u32, u32, vp]
     lib.tn_automorphism_dev.argtypes = [vp, vp, vp, sz, ctypes.POINTER(u32), sz, vp]
     lib.tn_automorphism_prepared_dev.argtypes = [vp, vp, vp, sz, ctypes.POINTER(u32), sz, vp]
     lib.tn_schoolbook_dev.argtypes = [vp, vp, vp, vp, sz, vp]
@@ -645,6 +646,46 @@ class Plan:
             step_key = PreparedOperand(self, prepared.tensor[k * key:(k + 1) * key], key)
             acc = self.poly_cmux_rotate_prepared(acc, exps[k], step_key, terms, base_log, balanced, out=bufs[k & 1], stream=stream)
         return acc
+
+    def poly_blind_rotate_prepared(self, acc, exps, prepared: PreparedOperand, terms, base_log, balanced=False, out=None, stream=None):
+        """A blind rotation from ONE launch (tn_poly_blind_rotate_prepared_dev): the steps of blind_rotate with the accumulator
+        kept on chip across them, bit-identical to that loop.  acc is a device tensor (batch, 2, n), left as it is unless out is
+        acc; exps is (steps, batch), a device tensor of 32-bit integers or host integers; prepared holds steps * 4 * terms rows,
+        one shared key per step.  out may be acc itself (in place) or another tensor of its shape that does not overlap it.
+        Shapes whose accumulator does not fit a workgroup's LDS (n = 8192 with 64-bit words) raise TN_EUNSUPPORTED: use
+        blind_rotate."""
+        import torch
+        self._own_prepared(prepared, "poly_blind_rotate_prepared", "key")
+        if not _is_torch(acc) or acc.dim() != 3 or acc.shape[-1] != self.n or acc.shape[1] == 0:
+            raise ValueError(f"Expected acc as a device tensor of shape (batch, 2, {self.n})")
+        if not acc.is_contiguous():
+            raise TinyNttError(TN_EINVAL, f"acc: need a contiguous tensor of {self.elem_bytes}-byte integers")
+        batch, comps, terms = int(acc.shape[0]), int(acc.shape[1]), int(terms)
+        self._dev_rows(acc.reshape(batch * comps, self.n), "acc")
+        if terms < 1:
+            raise ValueError(f"Expected terms >= 1, got {terms}")
+        if _is_torch(exps):
+            if exps.dim() != 2 or int(exps.shape[1]) != batch:
+                raise ValueError(f"Expected exps of shape (steps, {batch})")
+            steps = int(exps.shape[0])
+            e = self._exps(exps, steps * batch, acc.device)
+        else:
+            h = np.asarray(exps)
+            if h.ndim != 2 or h.shape[1] != batch:
+                raise ValueError(f"Expected exps of shape (steps, {batch})")
+            steps = int(h.shape[0])
+            e = self._exps(h.reshape(-1), steps * batch, acc.device)
+        key = comps * comps * terms
+        if prepared.rows != steps * key:
+            raise ValueError(f"Expected a key of {steps} x {key} rows, got {prepared.rows}")
+        c = out if out is not None else torch.empty_like(acc)
+        if not _is_torch(c) or c.numel() != batch * comps * self.n or not c.is_contiguous():
+            raise ValueError(f"Expected an output of {batch} x {comps} rows of {self.n} coefficients")
+        self._dev_rows(c.reshape(batch * comps, self.n), "out")
+        _check(self._lib, self._lib.tn_poly_blind_rotate_prepared_dev(self._h, acc.data_ptr(), e.data_ptr(), prepared.tensor.data_ptr(), c.data_ptr(),
+                                                                      batch, comps, steps, terms, int(base_log),
+                                                                      GADGET_BALANCED if balanced else 0, self._stream_ptr(stream)))
+        return c
 
     # ---- ring automorphisms a(x) -> a(x^g) ----------------------------------------
     @staticmethod
