@@ -1,5 +1,5 @@
 // emu_blindrot.cpp — TEST INFRASTRUCTURE: steps the blind-rotation kernel (polydot_blindrot_kernel:
-// tiny_ntt_amd/csrc/kernels_blindrot.hip) on the CPU, one emulated thread at a time, with the Stepper of ../emu/emu_stepper.h and
+// tiny_ntt_amd/csrc/kernels_blindrot.hip) on the CPU, one emulated thread at a time, with the Stepper of emu_stepper.h and
 // the headers the gfx950 kernel is compiled from (fused_core.h, cmux_core.h, launch_plan.h).  One emulated workgroup takes the
 // rows in turn, as a persistent workgroup does, with the accumulator in an LDS image of two rows that lives across steps AND
 // rows: the first row is loaded before the loop, a later row where the last step of the row before it would write its result
@@ -8,23 +8,14 @@
 // another thread's rotated read of the same step changes the result.  On top of that every word of the image carries the step
 // it was written for, and each read and write checks it (code 9): a rotated or own read of step k must see a word written for
 // step k, a write-back of step k comes only when all 2 n rotated reads of step k have happened.
-// Also the entry point's argument list (csrc/api_checks.h: check_blind_rotate) and the LDS rule (launch_plan.h) for the CPU.  A
-// library of its own, _build/libemu_blindrot.so (tests/test_blindrot_emu.py, tests/test_gpu_blindrot.py); with
-// -DEMU_BLINDROT_MAIN a stand-alone program for the sanitizers (make sanitize).
-#include "../emu/emu_stepper.h"
+// Also the entry point's argument list (csrc/api_checks.h: check_blind_rotate) and the LDS rule (launch_plan.h) for the CPU.
+// Part of tests/emu/_build/libemu.so (tests/test_blindrot_emu.py, tests/test_gpu_blindrot.py); with -DEMU_SANITIZE_CASES its
+// cases for tests/emu/sanitize_driver.cpp (make sanitize).
+#include "emu_stepper.h"
 #include "../../tiny_ntt_amd/csrc/cmux_core.h"
-#include "../../tiny_ntt_amd/csrc/api_checks.h"
-#include <cstdio>
 #include <string>
 
 namespace {
-
-// what the gadget calls refuse (csrc/api_checks.h: ApiCheck::gadget)
-bool gadget_ok(u64 q, size_t terms, u32 base_log, u32 flags) {
-  if (terms == 0 || (flags & ~1u)) return false;
-  if (base_log == 0 || base_log >= 64 || (((u64)1) << base_log) >= q) return false;
-  return terms - 1 <= 63 / base_log;
-}
 
 // a, c: [batch][2][n]; exps: [steps][batch]; bhat: [steps][2][2][terms][n]
 template <typename Sh, bool BC>
@@ -35,13 +26,13 @@ int polydot_blindrot_emu(const HostTables& t, const u64* a, const u32* exps, con
   typedef Policy<E, Sh::LAZY> Pol;
   typedef Stepper<E, LOGN, Sh::LPT, Pol, BC> S;
   typedef typename S::Cfg Cfg;
-  static_assert(Cfg::R <= 32, "one carry bit per word of the thread in a 32-bit mask");
   if (!blindrot_lds_fits<Sh>()) return 8;
   constexpr u32 EMASK = 2u * (u32)Cfg::N - 1u, NMASK = (u32)Cfg::N - 1u, N = (u32)Cfg::N;
   const FusedProductSetup<E> su = fused_product_setup(h_make_arith<E>(t), BC, false);
   S wg{su.ar};
   const typename S::Table fwd(t, su.fwd), inv(t, su.inv);
-  std::vector<typename S::Regs> xw(S::T), xa(S::T), xb(S::T), acc0(S::T), acc1(S::T);
+  std::vector<typename S::Regs> xw(S::T), acc0(S::T), acc1(S::T);
+  std::vector<typename S::Regs>* const sums[2] = {&acc0, &acc1};
   std::vector<u32> carries(S::T);
   std::vector<E> lds_acc(2 * (size_t)N);                       // the accumulator: component o at [o * N]
   std::vector<u32> written_for(2 * (size_t)N);                 // the step each word was written for (a row's load: step 0)
@@ -82,35 +73,12 @@ int polydot_blindrot_emu(const HostTables& t, const u64* a, const u32* exps, con
           carries[tau] = 0;                                    // carries never run from one polynomial into the next
         }
         for (size_t j = 0; j < terms; ++j, ++term) {
-          const u32 shift = (u32)j * base_log;
-          for (u32 tau = 0; tau < S::T; ++tau) {
-            u32 next_carries = 0;
-            for (int r = 0; r < Cfg::R; ++r) {
-              u32 cy = (carries[tau] >> r) & 1u;
-              xa[tau].x[r] = gadget_digit<E>(xw[tau].x[r], shift, base_log, balanced, cy, wg.ar.q);
-              next_carries |= cy << r;
-            }
-            carries[tau] = next_carries;
-          }
-          wg.forward(xa, fwd);                                 // once per term, for both components (barriers inside)
-          for (size_t o = 0; o < 2; ++o) {
-            const size_t boff = (key + o * comp + term) << LOGN;
-            for (u32 tau = 0; tau < S::T; ++tau) {
-              for (int r = 0; r < Cfg::R; ++r) xb[tau].x[r] = (E)bhat[boff + Cfg::prep_idx(tau, (u32)r)];
-              const typename S::Tw* zeta = wg.pre[tau].t + Cfg::pre_off(LOGN - 1);      // the zeta records came with the forward's
-              if (o == 0) {                                    // the digit row is needed again
-                dot_product_into<E, Cfg, Pol, BC>(acc0[tau].x, xa[tau].x, xb[tau].x, zeta, wg.ar, [](auto) {});
-              } else {                                         // the last component may overwrite it
-                if constexpr (BC) basecase<Cfg, Pol>(xa[tau].x, xb[tau].x, zeta, wg.ar);
-                else pointwise<E, Cfg, Pol>(xa[tau].x, xb[tau].x, wg.ar);
-                dot_accumulate<E, Cfg, Pol>(acc1[tau].x, xa[tau].x, wg.ar);
-              }
-            }
-          }
+          const size_t boff[2] = {key + term, key + comp + term};
+          gadget_term_step(wg, fwd, xw, carries, j, base_log, balanced, bhat, 2, boff, sums);      // (barriers inside)
         }
       }
       for (u32 o = 0; o < 2; ++o) {
-        std::vector<typename S::Regs>& acc = o == 0 ? acc0 : acc1;
+        std::vector<typename S::Regs>& acc = *sums[o];
         wg.inverse(acc, inv);                                  // (barriers inside: every rotated read of the step lies before them)
         for (u32 tau = 0; tau < S::T; ++tau) {
           if (rotated_reads[0] != N || rotated_reads[1] != N) hazard = 9;      // hazard (1)
@@ -147,8 +115,8 @@ int emu_poly_blind_rotate_prepared(uint32_t n, uint64_t q, uint64_t psi, int can
                                    uint64_t* c, size_t batch, size_t steps, size_t terms, uint32_t base_log, uint32_t flags) {
   if (!a || !exps || steps == 0) return 3;
   if (!params_ok(n, q, psi)) return 2;
-  if (!gadget_ok(q, terms, base_log, flags)) return 4;
   const HostTables t = h_build_tables(n, q, psi, !(canonical & 1));
+  if (!gadget_ok(t, terms, base_log, flags)) return 4;
   const bool bal = (flags & 1u) != 0;
   return emu_with_shape(t, [&](auto sh, auto bc) {
     return polydot_blindrot_emu<decltype(sh), decltype(bc)::value>(t, a, exps, bhat, c, batch, steps, terms, base_log, bal);
@@ -179,28 +147,20 @@ int emu_blindrot_api_check(uint32_t n, int elem_bytes, int has_fused, int omega_
                            const void* bhat, const void* c, size_t batch, size_t comps, size_t steps, size_t terms, uint32_t base_log, uint32_t flags,
                            int* launch, char* msg, size_t msg_len) {
   ApiCheck k{ApiPlan{n, elem_bytes, has_fused != 0, omega_only != 0, q, lazy != 0}, "tn_poly_blind_rotate_prepared_dev"};
-  const bool go = check_blind_rotate(k, a, exps, bhat, c, batch, comps, steps, terms, base_log, flags);
-  if (launch) *launch = go ? 1 : 0;
-  if (msg && msg_len) std::snprintf(msg, msg_len, "%s", k.msg.c_str());
-  return (int)k.st;
+  return api_answer(k, check_blind_rotate(k, a, exps, bhat, c, batch, comps, steps, terms, base_log, flags), launch, msg, msg_len);
 }
 
 }  // extern "C"
 
-#ifdef EMU_BLINDROT_MAIN
-// The stand-alone program of `make sanitize`: the stepping at the smallest shape of either lane width and at the base-case
+#ifdef EMU_SANITIZE_CASES
+#include "sanitize_cases.h"
+// The cases sanitize_driver.cpp runs (blindrot_cases): the stepping at the smallest shape of either lane width and at the base-case
 // shape, both policies, batch 5 (one workgroup takes all five rows: four reloads of the accumulator), 3 steps x 2 terms, both
 // digit modes, in place and out of place, with the exponents 0, 1, n, 2n - 1 and an unreduced one in step 0 and others behind.
 // Properties that need no second implementation of the transforms: keys of zero rows return a mod q; exponents of 0 return a
 // mod q whatever the keys; and three steps from one call equal three calls of one step each, where the accumulator goes
 // through memory.  Then the LDS rule and the argument list on made-up addresses.
 namespace {
-
-int checks = 0, failures = 0;
-void expect(bool ok, const char* what) {
-  ++checks;
-  if (!ok) { ++failures; std::printf("FAILED: %s\n", what); }
-}
 
 void stepping_cases(uint32_t n, uint64_t q, uint64_t psi) {
   const size_t batch = 5, terms = 2, steps = 3;
@@ -303,14 +263,12 @@ void api_cases() {
 
 }  // namespace
 
-int main() {
+void blindrot_cases() {
   const uint64_t q60 = 1152921504606830593ull, psi4096 = 431606828070683274ull;
   stepping_cases(256, 8380417, 1239911);
   stepping_cases(256, q60, h_powmod(psi4096, 16, q60));
   stepping_cases(4096, q60, psi4096);
   lds_cases();
   api_cases();
-  std::printf("%d checks, %d failures\n", checks, failures);
-  return failures ? 1 : 0;
 }
 #endif

@@ -1,26 +1,17 @@
 // emu_cmux.cpp — TEST INFRASTRUCTURE: steps the CMux rotation kernel (polydot_cmux_kernel: tiny_ntt_amd/csrc/kernels_cmux.hip) on
-// the CPU, one emulated thread at a time, with the Stepper of ../emu/emu_stepper.h and the headers the gfx950 kernel is compiled
+// the CPU, one emulated thread at a time, with the Stepper of emu_stepper.h and the headers the gfx950 kernel is compiled
 // from (fused_core.h, cmux_core.h): the exponent masked to 2n; per input polynomial the rotated-minus-own words (cmux_word on
-// the word at the masked rotated index and the thread's own word) and a carry mask of its own; per term gadget_digit, ONE
+// the word at the masked rotated index and the thread's own word) and a carry mask of its own; per term (gadget_term_step) gadget_digit, ONE
 // forward transform, component 0's product through dot_product_into and component 1's in place; two inverses; the add-in of
 // a[row][o] (cmux_add_in).  Also the monomial product in plain C++ from the definition of include/tinyntt.h, and the two entry
-// points' argument lists (csrc/api_checks.h: check_monomial, check_cmux_rotate) for the CPU.  A library of its own,
-// _build/libemu_cmux.so (tests/test_cmux_emu.py, tests/test_gpu_cmux.py); with -DEMU_CMUX_MAIN a stand-alone program for the
-// sanitizers (make sanitize).
-#include "../emu/emu_stepper.h"
+// points' argument lists (csrc/api_checks.h: check_monomial, check_cmux_rotate) for the CPU.  Part of
+// tests/emu/_build/libemu.so (tests/test_cmux_emu.py, tests/test_gpu_cmux.py); with -DEMU_SANITIZE_CASES its cases for
+// tests/emu/sanitize_driver.cpp (make sanitize).
+#include "emu_stepper.h"
 #include "../../tiny_ntt_amd/csrc/cmux_core.h"
-#include "../../tiny_ntt_amd/csrc/api_checks.h"
-#include <cstdio>
 #include <string>
 
 namespace {
-
-// what the gadget calls refuse (csrc/api_checks.h: ApiCheck::gadget)
-bool gadget_ok(u64 q, size_t terms, u32 base_log, u32 flags) {
-  if (terms == 0 || (flags & ~1u)) return false;
-  if (base_log == 0 || base_log >= 64 || (((u64)1) << base_log) >= q) return false;
-  return terms - 1 <= 63 / base_log;
-}
 
 // a, c: [batch][2][n]; exps: [batch]; bhat: [sets][2][2][terms][n]
 template <typename Sh, bool BC>
@@ -31,12 +22,12 @@ int polydot_cmux_emu(const HostTables& t, const u64* a, const u32* exps, const u
   typedef Policy<E, Sh::LAZY> Pol;
   typedef Stepper<E, LOGN, Sh::LPT, Pol, BC> S;
   typedef typename S::Cfg Cfg;
-  static_assert(Cfg::R <= 32, "one carry bit per word of the thread in a 32-bit mask");
   constexpr u32 EMASK = 2u * (u32)Cfg::N - 1u;
   const FusedProductSetup<E> su = fused_product_setup(h_make_arith<E>(t), BC, false);
   S wg{su.ar};
   const typename S::Table fwd(t, su.fwd), inv(t, su.inv);
-  std::vector<typename S::Regs> xw(S::T), xa(S::T), xb(S::T), acc0(S::T), acc1(S::T);
+  std::vector<typename S::Regs> xw(S::T), acc0(S::T), acc1(S::T);
+  std::vector<typename S::Regs>* const sums[2] = {&acc0, &acc1};
   std::vector<u32> carries(S::T);
   const size_t ins = 2, comp = ins * terms;                  // prepared rows of one component of a set
   for (size_t row = 0; row < batch; ++row) {
@@ -57,35 +48,12 @@ int polydot_cmux_emu(const HostTables& t, const u64* a, const u32* exps, const u
         carries[tau] = 0;                                    // carries never run from one polynomial into the next
       }
       for (size_t j = 0; j < terms; ++j, ++term) {
-        const u32 shift = (u32)j * base_log;
-        for (u32 tau = 0; tau < S::T; ++tau) {
-          u32 next_carries = 0;
-          for (int r = 0; r < Cfg::R; ++r) {
-            u32 cy = (carries[tau] >> r) & 1u;
-            xa[tau].x[r] = gadget_digit<E>(xw[tau].x[r], shift, base_log, balanced, cy, wg.ar.q);
-            next_carries |= cy << r;
-          }
-          carries[tau] = next_carries;
-        }
-        wg.forward(xa, fwd);                                 // once per term, for both components
-        for (size_t o = 0; o < 2; ++o) {
-          const size_t boff = (set + o * comp + term) << LOGN;
-          for (u32 tau = 0; tau < S::T; ++tau) {
-            for (int r = 0; r < Cfg::R; ++r) xb[tau].x[r] = (E)bhat[boff + Cfg::prep_idx(tau, (u32)r)];
-            const typename S::Tw* zeta = wg.pre[tau].t + Cfg::pre_off(LOGN - 1);      // the zeta records came with the forward's
-            if (o == 0) {                                    // the digit row is needed again
-              dot_product_into<E, Cfg, Pol, BC>(acc0[tau].x, xa[tau].x, xb[tau].x, zeta, wg.ar, [](auto) {});
-            } else {                                         // the last component may overwrite it
-              if constexpr (BC) basecase<Cfg, Pol>(xa[tau].x, xb[tau].x, zeta, wg.ar);
-              else pointwise<E, Cfg, Pol>(xa[tau].x, xb[tau].x, wg.ar);
-              dot_accumulate<E, Cfg, Pol>(acc1[tau].x, xa[tau].x, wg.ar);
-            }
-          }
-        }
+        const size_t boff[2] = {set + term, set + comp + term};
+        gadget_term_step(wg, fwd, xw, carries, j, base_log, balanced, bhat, 2, boff, sums);
       }
     }
     for (size_t o = 0; o < 2; ++o) {
-      std::vector<typename S::Regs>& acc = o == 0 ? acc0 : acc1;
+      std::vector<typename S::Regs>& acc = *sums[o];
       wg.inverse(acc, inv);
       const u64* arow = a + ((row * 2 + o) << LOGN);         // read again for the add-in
       for (u32 tau = 0; tau < S::T; ++tau)
@@ -111,8 +79,8 @@ int emu_poly_cmux_rotate_prepared(uint32_t n, uint64_t q, uint64_t psi, int cano
   if (bhat_sets != 1 && bhat_sets != batch) return 3;
   if (!a || !exps) return 3;
   if (!params_ok(n, q, psi)) return 2;
-  if (!gadget_ok(q, terms, base_log, flags)) return 4;
   const HostTables t = h_build_tables(n, q, psi, !(canonical & 1));
+  if (!gadget_ok(t, terms, base_log, flags)) return 4;
   const bool bal = (flags & 1u) != 0;
   return emu_with_shape(t, [&](auto sh, auto bc) {
     return polydot_cmux_emu<decltype(sh), decltype(bc)::value>(t, a, exps, bhat, bhat_sets, c, batch, terms, base_log, bal);
@@ -147,38 +115,27 @@ int emu_monomial_mul(uint32_t n, uint64_t q, const uint64_t* a, const uint32_t* 
 int emu_monomial_api_check(uint32_t n, int elem_bytes, int has_fused, int omega_only, uint64_t q, const void* a, const void* exps, const void* out,
                            size_t batch, size_t group, uint32_t flags, int* launch, char* msg, size_t msg_len) {
   ApiCheck k{ApiPlan{n, elem_bytes, has_fused != 0, omega_only != 0, q}, "tn_monomial_mul_dev"};
-  const bool go = check_monomial(k, a, exps, out, batch, group, flags);
-  if (launch) *launch = go ? 1 : 0;
-  if (msg && msg_len) std::snprintf(msg, msg_len, "%s", k.msg.c_str());
-  return (int)k.st;
+  return api_answer(k, check_monomial(k, a, exps, out, batch, group, flags), launch, msg, msg_len);
 }
 
 int emu_cmux_api_check(uint32_t n, int elem_bytes, int has_fused, int omega_only, uint64_t q, const void* a, const void* exps, const void* bhat,
                        const void* c, size_t sets, size_t batch, size_t comps, size_t terms, uint32_t base_log, uint32_t flags, int* launch, char* msg,
                        size_t msg_len) {
   ApiCheck k{ApiPlan{n, elem_bytes, has_fused != 0, omega_only != 0, q}, "tn_poly_cmux_rotate_prepared_dev"};
-  const bool go = check_cmux_rotate(k, a, exps, bhat, sets, c, batch, comps, terms, base_log, flags);
-  if (launch) *launch = go ? 1 : 0;
-  if (msg && msg_len) std::snprintf(msg, msg_len, "%s", k.msg.c_str());
-  return (int)k.st;
+  return api_answer(k, check_cmux_rotate(k, a, exps, bhat, sets, c, batch, comps, terms, base_log, flags), launch, msg, msg_len);
 }
 
 }  // extern "C"
 
-#ifdef EMU_CMUX_MAIN
-// The stand-alone program of `make sanitize`: the stepping at the smallest shape of either lane width and at the base-case
+#ifdef EMU_SANITIZE_CASES
+#include "sanitize_cases.h"
+// The cases sanitize_driver.cpp runs (cmux_cases): the stepping at the smallest shape of either lane width and at the base-case
 // shape, both policies, batch 5 x 2 terms, one shared set and one per row, both digit modes, with the exponents 0, 1, n,
 // 2n - 1 and an unreduced one.  Two properties that need no second implementation of the transforms: with a key of zero rows
 // the step returns a mod q; and the step is linear in the key, c(b) + c(b') - a = c(b + b') mod q (prepared rows add
 // word-wise).  Then the monomial product against a second statement of the definition, and both argument lists on made-up
 // addresses.
 namespace {
-
-int checks = 0, failures = 0;
-void expect(bool ok, const char* what) {
-  ++checks;
-  if (!ok) { ++failures; std::printf("FAILED: %s\n", what); }
-}
 
 void stepping_cases(uint32_t n, uint64_t q, uint64_t psi) {
   const size_t batch = 5, terms = 2;
@@ -291,7 +248,7 @@ void api_cases() {
 
 }  // namespace
 
-int main() {
+void cmux_cases() {
   const uint64_t q60 = 1152921504606830593ull, psi4096 = 431606828070683274ull;
   stepping_cases(256, 8380417, 1239911);
   stepping_cases(256, q60, h_powmod(psi4096, 16, q60));
@@ -299,7 +256,5 @@ int main() {
   monomial_cases(16, 8380417);
   monomial_cases(256, q60);
   api_cases();
-  std::printf("%d checks, %d failures\n", checks, failures);
-  return failures ? 1 : 0;
 }
 #endif

@@ -8,16 +8,8 @@
 
 namespace {
 
-// what tn_gadget_decompose_dev / tn_poly_gadget_dot_prepared_dev refuse (csrc/api_checks.h: ApiCheck::gadget)
-bool gadget_ok(u64 q, size_t terms, u32 base_log, u32 flags) {
-  if (terms == 0 || (flags & ~1u)) return false;
-  if (base_log == 0 || base_log >= 64 || (((u64)1) << base_log) >= q) return false;
-  return terms - 1 <= 63 / base_log;
-}
-
-// Same steps as polydot_gadget_kernel: per output row the words of a are made canonical once (gadget_canon); every term cuts
-// its digit out of them (gadget_digit, the carries of the thread's words in one mask), runs one forward transform WITHOUT
-// load_reduce and the product against its prepared row; the products are summed by dot_accumulate and one inverse runs on the sum.
+// Same steps as polydot_gadget_kernel: per output row the words of a are made canonical once (gadget_canon); every term is
+// one gadget_term_step (emu_stepper.h) of one component; one inverse runs on the sum.
 template <typename Sh, bool BC>
 int polydot_gadget_emu(const HostTables& t, const u64* a, const u64* bhat, size_t bhat_sets, u64* c, size_t batch, size_t terms, u32 base_log,
                        bool balanced) {
@@ -26,11 +18,11 @@ int polydot_gadget_emu(const HostTables& t, const u64* a, const u64* bhat, size_
   typedef Policy<E, Sh::LAZY> Pol;
   typedef Stepper<E, LOGN, Sh::LPT, Pol, BC> S;
   typedef typename S::Cfg Cfg;
-  static_assert(Cfg::R <= 32, "one carry bit per word of the thread in a 32-bit mask");
   const FusedProductSetup<E> su = fused_product_setup(h_make_arith<E>(t), BC, false);
   S wg{su.ar};
   const typename S::Table fwd(t, su.fwd), inv(t, su.inv);
-  std::vector<typename S::Regs> xw(S::T), xa(S::T), xb(S::T), acc(S::T);
+  std::vector<typename S::Regs> xw(S::T), acc(S::T);
+  std::vector<typename S::Regs>* const sum[1] = {&acc};
   std::vector<u32> carries(S::T);
   for (size_t row = 0; row < batch; ++row) {
     for (u32 tau = 0; tau < S::T; ++tau) {
@@ -41,24 +33,8 @@ int polydot_gadget_emu(const HostTables& t, const u64* a, const u64* bhat, size_
       carries[tau] = 0;
     }
     for (size_t j = 0; j < terms; ++j) {
-      const size_t boff = ((bhat_sets == 1 ? 0 : row) * terms + j) << LOGN;
-      const u32 shift = (u32)j * base_log;
-      for (u32 tau = 0; tau < S::T; ++tau) {
-        u32 next_carries = 0;
-        for (int r = 0; r < Cfg::R; ++r) {
-          xb[tau].x[r] = (E)bhat[boff + Cfg::prep_idx(tau, (u32)r)];
-          u32 cy = (carries[tau] >> r) & 1u;
-          xa[tau].x[r] = gadget_digit<E>(xw[tau].x[r], shift, base_log, balanced, cy, wg.ar.q);
-          next_carries |= cy << r;
-        }
-        carries[tau] = next_carries;
-      }
-      wg.forward(xa, fwd);
-      for (u32 tau = 0; tau < S::T; ++tau) {
-        if constexpr (BC) basecase<Cfg, Pol>(xa[tau].x, xb[tau].x, wg.pre[tau].t + Cfg::pre_off(LOGN - 1), wg.ar);   // the zeta records came with the forward's
-        else pointwise<E, Cfg, Pol>(xa[tau].x, xb[tau].x, wg.ar);
-        dot_accumulate<E, Cfg, Pol>(acc[tau].x, xa[tau].x, wg.ar);
-      }
+      const size_t boff = (bhat_sets == 1 ? 0 : row) * terms + j;
+      gadget_term_step(wg, fwd, xw, carries, j, base_log, balanced, bhat, 1, &boff, sum);
     }
     wg.inverse(acc, inv);
     for (u32 tau = 0; tau < S::T; ++tau)
@@ -90,8 +66,8 @@ int emu_poly_gadget_dot_prepared(uint32_t n, uint64_t q, uint64_t psi, int canon
   if (bhat_sets != 1 && bhat_sets != batch) return 3;
   if (!a) return 3;
   if (!params_ok(n, q, psi)) return 2;
-  if (!gadget_ok(q, terms, base_log, flags)) return 4;
   const HostTables t = h_build_tables(n, q, psi, !(canonical & 1));
+  if (!gadget_ok(t, terms, base_log, flags)) return 4;
   const bool bal = (flags & 1u) != 0;
   return emu_with_shape(t, [&](auto sh, auto bc) {
     return polydot_gadget_emu<decltype(sh), decltype(bc)::value>(t, a, bhat, bhat_sets, c, batch, terms, base_log, bal);
@@ -104,8 +80,8 @@ int emu_poly_gadget_dot_prepared(uint32_t n, uint64_t q, uint64_t psi, int canon
 int emu_gadget_digits(uint32_t n, uint64_t q, uint64_t psi, int canonical, const uint64_t* x, uint64_t* digits, size_t count, size_t terms,
                       uint32_t base_log, uint32_t flags, int* lane_bytes, int* lazy) {
   if (!params_ok(n, q, psi)) return 2;
-  if (!gadget_ok(q, terms, base_log, flags)) return 4;
   const HostTables t = h_build_tables(n, q, psi, !(canonical & 1));
+  if (!gadget_ok(t, terms, base_log, flags)) return 4;
   if (lane_bytes) *lane_bytes = t.elem_bytes;
   if (lazy) *lazy = t.lazy ? 1 : 0;
   const bool bal = (flags & 1u) != 0;

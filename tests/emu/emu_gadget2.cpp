@@ -1,23 +1,14 @@
 // emu_gadget2.cpp — TEST INFRASTRUCTURE: steps the two-component gadget kernel (polydot_gadget2_kernel:
-// tiny_ntt_amd/csrc/kernels_gadget.hip) on the CPU, one emulated thread at a time, with the Stepper of ../emu/emu_stepper.h and
-// the headers the gfx950 kernel is compiled from: gadget_canon / gadget_digit, ONE forward transform per term, component 0's
+// tiny_ntt_amd/csrc/kernels_gadget.hip) on the CPU, one emulated thread at a time, with the Stepper of emu_stepper.h and
+// the headers the gfx950 kernel is compiled from: gadget_canon; per term (gadget_term_step) gadget_digit, ONE forward transform, component 0's
 // product through dot_product_into (the digit row left as it is), component 1's through the gadget kernel's in-place product,
 // two sums (dot_accumulate_one) and two inverses.  Also the new entry point's argument list (csrc/api_checks.h:
-// check_gadget_multidot) for the CPU.  A library of its own, _build/libemu_gadget2.so (tests/test_gadget2_emu.py,
-// tests/test_gpu_gadget2.py); with -DEMU_GADGET2_MAIN a stand-alone program for the sanitizers (make sanitize).
-#include "../emu/emu_stepper.h"
-#include "../../tiny_ntt_amd/csrc/api_checks.h"
-#include <cstdio>
+// check_gadget_multidot) for the CPU.  Part of tests/emu/_build/libemu.so (tests/test_gadget2_emu.py,
+// tests/test_gpu_gadget2.py); with -DEMU_SANITIZE_CASES its cases for tests/emu/sanitize_driver.cpp (make sanitize).
+#include "emu_stepper.h"
 #include <string>
 
 namespace {
-
-// what the gadget calls refuse (csrc/api_checks.h: ApiCheck::gadget)
-bool gadget_ok(u64 q, size_t terms, u32 base_log, u32 flags) {
-  if (terms == 0 || (flags & ~1u)) return false;
-  if (base_log == 0 || base_log >= 64 || (((u64)1) << base_log) >= q) return false;
-  return terms - 1 <= 63 / base_log;
-}
 
 // bhat: [sets][outs][terms][n]; c: [batch][outs][n].  outs == 1 is the gadget kernel's flow (one in-place product per term).
 template <typename Sh, bool BC>
@@ -28,11 +19,11 @@ int polydot_gadget2_emu(const HostTables& t, const u64* a, const u64* bhat, size
   typedef Policy<E, Sh::LAZY> Pol;
   typedef Stepper<E, LOGN, Sh::LPT, Pol, BC> S;
   typedef typename S::Cfg Cfg;
-  static_assert(Cfg::R <= 32, "one carry bit per word of the thread in a 32-bit mask");
   const FusedProductSetup<E> su = fused_product_setup(h_make_arith<E>(t), BC, false);
   S wg{su.ar};
   const typename S::Table fwd(t, su.fwd), inv(t, su.inv);
-  std::vector<typename S::Regs> xw(S::T), xa(S::T), xb(S::T), acc0(S::T), acc1(S::T);
+  std::vector<typename S::Regs> xw(S::T), acc0(S::T), acc1(S::T);
+  std::vector<typename S::Regs>* const sums[2] = {&acc0, &acc1};
   std::vector<u32> carries(S::T);
   for (size_t row = 0; row < batch; ++row) {
     for (u32 tau = 0; tau < S::T; ++tau) {
@@ -45,34 +36,11 @@ int polydot_gadget2_emu(const HostTables& t, const u64* a, const u64* bhat, size
     }
     const size_t set = (bhat_sets == 1 ? 0 : row) * outs * terms;
     for (size_t j = 0; j < terms; ++j) {
-      const u32 shift = (u32)j * base_log;
-      for (u32 tau = 0; tau < S::T; ++tau) {
-        u32 next_carries = 0;
-        for (int r = 0; r < Cfg::R; ++r) {
-          u32 cy = (carries[tau] >> r) & 1u;
-          xa[tau].x[r] = gadget_digit<E>(xw[tau].x[r], shift, base_log, balanced, cy, wg.ar.q);
-          next_carries |= cy << r;
-        }
-        carries[tau] = next_carries;
-      }
-      wg.forward(xa, fwd);                                   // once per term, for every component
-      for (size_t o = 0; o < outs; ++o) {
-        const size_t boff = (set + o * terms + j) << LOGN;
-        for (u32 tau = 0; tau < S::T; ++tau) {
-          for (int r = 0; r < Cfg::R; ++r) xb[tau].x[r] = (E)bhat[boff + Cfg::prep_idx(tau, (u32)r)];
-          const typename S::Tw* zeta = wg.pre[tau].t + Cfg::pre_off(LOGN - 1);      // the zeta records came with the forward's
-          if (o + 1 < outs) {                                // the kernel's component 0: the digit row is needed again
-            dot_product_into<E, Cfg, Pol, BC>(acc0[tau].x, xa[tau].x, xb[tau].x, zeta, wg.ar, [](auto) {});
-          } else {                                           // the last component may overwrite it: the gadget kernel's product
-            if constexpr (BC) basecase<Cfg, Pol>(xa[tau].x, xb[tau].x, zeta, wg.ar);
-            else pointwise<E, Cfg, Pol>(xa[tau].x, xb[tau].x, wg.ar);
-            dot_accumulate<E, Cfg, Pol>(outs == 1 ? acc0[tau].x : acc1[tau].x, xa[tau].x, wg.ar);
-          }
-        }
-      }
+      const size_t boff[2] = {set + j, set + terms + j};
+      gadget_term_step(wg, fwd, xw, carries, j, base_log, balanced, bhat, outs, boff, sums);
     }
     for (size_t o = 0; o < outs; ++o) {
-      std::vector<typename S::Regs>& acc = o == 0 ? acc0 : acc1;
+      std::vector<typename S::Regs>& acc = *sums[o];
       wg.inverse(acc, inv);
       for (u32 tau = 0; tau < S::T; ++tau)
         for (int r = 0; r < Cfg::R; ++r) c[((row * outs + o) << LOGN) + Cfg::jidx(0, tau, r)] = acc[tau].x[r];
@@ -94,8 +62,8 @@ int emu_poly_gadget_multidot_prepared(uint32_t n, uint64_t q, uint64_t psi, int 
   if (!a) return 3;
   if (outs != 1 && outs != 2) return 5;
   if (!params_ok(n, q, psi)) return 2;
-  if (!gadget_ok(q, terms, base_log, flags)) return 4;
   const HostTables t = h_build_tables(n, q, psi, !(canonical & 1));
+  if (!gadget_ok(t, terms, base_log, flags)) return 4;
   const bool bal = (flags & 1u) != 0;
   return emu_with_shape(t, [&](auto sh, auto bc) {
     return polydot_gadget2_emu<decltype(sh), decltype(bc)::value>(t, a, bhat, bhat_sets, c, batch, outs, terms, base_log, bal);
@@ -109,25 +77,17 @@ int emu_gadget2_api_check(uint32_t n, int elem_bytes, int has_fused, int omega_o
                           size_t sets, size_t batch, size_t outs, size_t terms, uint32_t base_log, uint32_t flags, int* launch, char* msg,
                           size_t msg_len) {
   ApiCheck k{ApiPlan{n, elem_bytes, has_fused != 0, omega_only != 0, q}, "tn_poly_gadget_multidot_prepared_dev"};
-  const bool go = check_gadget_multidot(k, a, bhat, sets, c, batch, outs, terms, base_log, flags);
-  if (launch) *launch = go ? 1 : 0;
-  if (msg && msg_len) std::snprintf(msg, msg_len, "%s", k.msg.c_str());
-  return (int)k.st;
+  return api_answer(k, check_gadget_multidot(k, a, bhat, sets, c, batch, outs, terms, base_log, flags), launch, msg, msg_len);
 }
 
 }  // extern "C"
 
-#ifdef EMU_GADGET2_MAIN
-// The stand-alone program of `make sanitize`: the stepping at the smallest shape of either lane width and at the base-case
+#ifdef EMU_SANITIZE_CASES
+#include "sanitize_cases.h"
+// The cases sanitize_driver.cpp runs (gadget2_cases): the stepping at the smallest shape of either lane width and at the base-case
 // shape, both policies, batch 2 x 2 terms, one shared set and one per row, both digit modes, each pair compared with the
 // one-component stepping of its slices; then the argument list on made-up addresses.
 namespace {
-
-int checks = 0, failures = 0;
-void expect(bool ok, const char* what) {
-  ++checks;
-  if (!ok) { ++failures; std::printf("FAILED: %s\n", what); }
-}
 
 void stepping_cases(uint32_t n, uint64_t q, uint64_t psi) {
   const size_t batch = 2, terms = 2;
@@ -188,13 +148,11 @@ void api_cases() {
 
 }  // namespace
 
-int main() {
+void gadget2_cases() {
   const uint64_t q60 = 1152921504606830593ull, psi4096 = 431606828070683274ull;
   stepping_cases(256, 8380417, 1239911);
   stepping_cases(256, q60, h_powmod(psi4096, 16, q60));
   stepping_cases(4096, q60, psi4096);
   api_cases();
-  std::printf("%d checks, %d failures\n", checks, failures);
-  return failures ? 1 : 0;
 }
 #endif

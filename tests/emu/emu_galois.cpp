@@ -2,12 +2,10 @@
 // tiny_ntt_amd/csrc/kernels_galois.hip) on the CPU with the header they are compiled from (csrc/galois_core.h): per tile of rows
 // the staging half for every thread of the workgroup, then the gather half for every thread, on an LDS image of exactly the
 // size the launcher asks for.  Also the index maps by themselves and the entry points' argument list (csrc/api_checks.h:
-// check_automorphism) for the CPU.  A library of its own, _build/libemu_galois.so (tests/test_galois_emu.py,
-// tests/test_gpu_galois.py); with -DEMU_GALOIS_MAIN a stand-alone program for the sanitizers (make sanitize).
-#include "../emu/emu_stepper.h"
+// check_automorphism) for the CPU.  Part of tests/emu/_build/libemu.so (tests/test_galois_emu.py,
+// tests/test_gpu_galois.py); with -DEMU_SANITIZE_CASES its cases for tests/emu/sanitize_driver.cpp (make sanitize).
+#include "emu_stepper.h"
 #include "../../tiny_ntt_amd/csrc/galois_core.h"
-#include "../../tiny_ntt_amd/csrc/api_checks.h"
-#include <cstdio>
 #include <string>
 
 namespace {
@@ -131,28 +129,20 @@ uint32_t emu_galois_tile_rows(uint32_t logn) { return galois_tile_rows(logn); }
 int emu_galois_api_check(uint32_t n, int elem_bytes, int has_fused, int omega_only, uint64_t q, int prepared, const void* in, const void* out,
                          size_t batch, const uint32_t* galois, size_t count, int* launch, char* msg, size_t msg_len) {
   ApiCheck k{ApiPlan{n, elem_bytes, has_fused != 0, omega_only != 0, q}, prepared ? "tn_automorphism_prepared_dev" : "tn_automorphism_dev"};
-  const bool go = check_automorphism(k, in, out, batch, galois, count, prepared != 0);
-  if (launch) *launch = go ? 1 : 0;
-  if (msg && msg_len) std::snprintf(msg, msg_len, "%s", k.msg.c_str());
-  return (int)k.st;
+  return api_answer(k, check_automorphism(k, in, out, batch, galois, count, prepared != 0), launch, msg, msg_len);
 }
 
 }  // extern "C"
 
-#ifdef EMU_GALOIS_MAIN
-// The stand-alone program of `make sanitize`: both kernels stepped over every tile shape (several rows per tile with a last
+#ifdef EMU_SANITIZE_CASES
+#include "sanitize_cases.h"
+// The cases sanitize_driver.cpp runs (galois_cases): both kernels stepped over every tile shape (several rows per tile with a last
 // tile that is not full, one row per tile) at both lane widths, the prepared kernel on every fused n = 256 .. 8192, both policies
 // and the base case, every named element and a repeated one; then the argument list.  The coefficient results are compared
 // with the definition written out here.  The prepared results are only checked to come back under sigma_{g^-1}: any invertible
 // wrong permutation would pass that, so for the prepared kernel this program is a MEMORY-SAFETY run (every index inside the
 // image, the factor table, the input and the output); that its words are right is tests/test_galois_emu.py's to show.
 namespace {
-
-int checks = 0, failures = 0;
-void expect(bool ok, const char* what) {
-  ++checks;
-  if (!ok) { ++failures; std::printf("FAILED: %s\n", what); }
-}
 
 uint64_t lcg = 88172645463325252ull;
 uint64_t rnd() { lcg = lcg * 6364136223846793005ull + 1442695040888963407ull; return lcg; }
@@ -188,7 +178,7 @@ void coefficient_cases(uint32_t n, uint64_t q) {
 
 void prepared_cases(uint32_t n, uint64_t q, uint64_t psi) {
   const uint32_t logn = (uint32_t)__builtin_ctz(n);
-  const int before = failures;
+  const int before = tally.failures;
   for (int canonical = 0; canonical < 2; ++canonical)
     for (size_t rows : {(size_t)1, (size_t)5})
       for (size_t count : {(size_t)1, (size_t)3}) {
@@ -206,7 +196,7 @@ void prepared_cases(uint32_t n, uint64_t q, uint64_t psi) {
           }
         expect(back, "sigma_g then sigma_{g^-1} gives the prepared row back");
       }
-  std::printf("prepared n=%u q=%llu both policies: %s\n", n, (unsigned long long)q, failures == before ? "ok" : "FAILED");
+  std::printf("prepared n=%u q=%llu both policies: %s\n", n, (unsigned long long)q, tally.failures == before ? "ok" : "FAILED");
 }
 
 void api_cases() {
@@ -244,7 +234,7 @@ void api_cases() {
 
 }  // namespace
 
-int main() {
+void galois_cases() {
   const uint64_t q23 = 8380417, q60 = 1152921504606830593ull, psi4096 = 431606828070683274ull;
   for (uint32_t n : {4u, 8u, 64u, 256u, 1024u, 4096u, 8192u}) {
     coefficient_cases(n, q23);                                                // (no psi: the kernel needs n and q alone)
@@ -257,7 +247,5 @@ int main() {
   prepared_cases(8192, q60, 458558429756866ull);                             // the largest image: 64 KiB
   prepared_cases(8192, 2147352577ull, 44302);                                // 2^31 - 131071 = 1 mod 16384
   api_cases();
-  std::printf("%d checks, %d failures\n", checks, failures);
-  return failures ? 1 : 0;
 }
 #endif

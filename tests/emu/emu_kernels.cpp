@@ -459,9 +459,7 @@ int emu_api_check(const char* entry, uint32_t n, int elem_bytes, int has_fused, 
   else if (e == "tn_fill_lcg_dev") go = check_fill(k, out != nullptr, batch);
   else if (e == "tn_checksum_rows_dev") go = check_fill(k, a && out, batch);
   else return -1;
-  if (launch) *launch = go ? 1 : 0;
-  if (msg && msg_len) std::snprintf(msg, msg_len, "%s", k.msg.c_str());
-  return (int)k.st;
+  return api_answer(k, go, launch, msg, msg_len);
 }
 
 }  // extern "C"

@@ -2,13 +2,16 @@
 // kernels' per-thread code (tiny_ntt_amd/csrc/fused_core.h, modarith.h, plan_tables.h: the very headers the gfx950 kernels
 // are compiled from), one emulated thread at a time with the LDS image between phases.  emu_with_shape picks the instantiation
 // for a plan through the launchers' own dispatcher and base-case rule (launch_plan.h: with_fused_shape, fused_use_bc), so
-// tests/emu names no shape.  Included by emu_kernels.cpp, emu_prepared.cpp, emu_dot.cpp, emu_hat.cpp and emu_gadget.cpp,
-// which tests/emu/Makefile links into one libemu.so.
+// tests/emu names no shape.  gadget_ok and api_answer put the library's own argument checks (csrc/api_checks.h) behind the
+// stepping entry points, which restate no bound of the library.  Included by every emu_*.cpp of this directory (kernels,
+// prepared, dot, hat, gadget, gadget2, galois, extprod, cmux, blindrot), which tests/emu/Makefile links into one libemu.so.
 #pragma once
 #include <stdint.h>
 #include <stddef.h>
+#include <cstdio>
 #include <vector>
 #include "../../tiny_ntt_amd/csrc/plan_tables.h"
+#include "../../tiny_ntt_amd/csrc/api_checks.h"
 
 using namespace tn;
 
@@ -75,6 +78,46 @@ template <typename E, int LOGN, int LPT, typename Pol, bool BC = false> struct S
   }
 };
 
+// One term of the gadget kernels (polydot_gadget_kernel, ..._gadget2_, ..._extprod_, ..._cmux_, ..._blindrot_kernel) for every
+// thread of the workgroup: digit j is cut out of the thread's put-away words xw (gadget_digit, the carries of the thread's
+// words in one mask that is handed on to the next term), ONE forward transform runs WITHOUT load_reduce, then one product per
+// component against its prepared row bhat[boff[o] << LOGN ...]: every component but the last through dot_product_into, which
+// leaves the digit row as it is for the next one; the last in place (the gadget kernel's product) and through dot_accumulate.
+// Component o is summed into *acc[o].  How xw is put away and what happens to the sums is the family's own.
+template <typename E, int LOGN, int LPT, typename Pol, bool BC>
+void gadget_term_step(Stepper<E, LOGN, LPT, Pol, BC>& wg, const typename Stepper<E, LOGN, LPT, Pol, BC>::Table& fwd,
+                      const std::vector<typename Stepper<E, LOGN, LPT, Pol, BC>::Regs>& xw, std::vector<u32>& carries, size_t j, u32 base_log,
+                      bool balanced, const u64* bhat, size_t comps, const size_t* boff,
+                      std::vector<typename Stepper<E, LOGN, LPT, Pol, BC>::Regs>* const* acc) {
+  typedef Stepper<E, LOGN, LPT, Pol, BC> S;
+  typedef typename S::Cfg Cfg;
+  static_assert(Cfg::R <= 32, "one carry bit per word of the thread in a 32-bit mask");
+  std::vector<typename S::Regs> xa(S::T), xb(S::T);
+  const u32 shift = (u32)j * base_log;
+  for (u32 tau = 0; tau < S::T; ++tau) {
+    u32 next_carries = 0;
+    for (int r = 0; r < Cfg::R; ++r) {
+      u32 cy = (carries[tau] >> r) & 1u;
+      xa[tau].x[r] = gadget_digit<E>(xw[tau].x[r], shift, base_log, balanced, cy, wg.ar.q);
+      next_carries |= cy << r;
+    }
+    carries[tau] = next_carries;
+  }
+  wg.forward(xa, fwd);                                       // once per term, for every component
+  for (size_t o = 0; o < comps; ++o)
+    for (u32 tau = 0; tau < S::T; ++tau) {
+      for (int r = 0; r < Cfg::R; ++r) xb[tau].x[r] = (E)bhat[(boff[o] << LOGN) + Cfg::prep_idx(tau, (u32)r)];
+      const typename S::Tw* zeta = wg.pre[tau].t + Cfg::pre_off(LOGN - 1);      // the zeta records came with the forward's
+      if (o + 1 < comps) {                                   // the digit row is needed again
+        dot_product_into<E, Cfg, Pol, BC>((*acc[o])[tau].x, xa[tau].x, xb[tau].x, zeta, wg.ar, [](auto) {});
+      } else {                                               // the last component may overwrite it
+        if constexpr (BC) basecase<Cfg, Pol>(xa[tau].x, xb[tau].x, zeta, wg.ar);
+        else pointwise<E, Cfg, Pol>(xa[tau].x, xb[tau].x, wg.ar);
+        dot_accumulate<E, Cfg, Pol>((*acc[o])[tau].x, xa[tau].x, wg.ar);
+      }
+    }
+}
+
 inline bool params_ok(u32 n, u64 q, u64 psi) {
   if (n < 4 || (n & (n - 1)) || q < 3 || !(q & 1) || q >= ((u64)1 << 62)) return false;
   return h_powmod(psi % q, n, q) == q - 1;
@@ -89,6 +132,21 @@ int emu_with_shape(const HostTables& t, F&& f) {
     if constexpr (Sh::HAS_BC) { if (fused_use_bc<Sh>(t.bc_ok)) return f(sh, std::true_type()); }
     return f(sh, std::false_type());
   });
+}
+
+// What the gadget calls refuse of (terms, base_log, flags) for a plan: ApiCheck::gadget itself, one row, so that its row limit
+// never speaks.  The stepping entry points answer 4 where it refuses.
+inline bool gadget_ok(const HostTables& t, size_t terms, u32 base_log, u32 flags) {
+  ApiCheck k{ApiPlan{t.n, t.elem_bytes, true, false, t.q}, "emu"};
+  return k.gadget(1, terms, base_log, flags);
+}
+
+// The end of every *_api_check entry point: the status; *launch = 1 when the call would go on to its launch; msg receives the
+// text tn_last_error would give.
+inline int api_answer(const ApiCheck& k, bool go, int* launch, char* msg, size_t msg_len) {
+  if (launch) *launch = go ? 1 : 0;
+  if (msg && msg_len) std::snprintf(msg, msg_len, "%s", k.msg.c_str());
+  return (int)k.st;
 }
 
 }  // namespace

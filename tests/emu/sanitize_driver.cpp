@@ -1,5 +1,7 @@
-// Test infrastructure: the CPU stepping of the kernels' per-thread code (emu_kernels.cpp, emu_prepared.cpp, emu_dot.cpp, emu_hat.cpp,
-// emu_gadget.cpp: the product's own headers compiled for the host) run under AddressSanitizer + UndefinedBehaviorSanitizer.  GPU sanitizers are not available on the GPU pool, so this is where an
+// Test infrastructure: the CPU stepping of the kernels' per-thread code (every emu_*.cpp of this directory: the product's own
+// headers compiled for the host) run under AddressSanitizer + UndefinedBehaviorSanitizer, one program with one tally.  The
+// cases of the first five families are below; those of emu_gadget2, emu_galois, emu_extprod, emu_cmux and emu_blindrot stand
+// in their sources (sanitize_cases.h) and are called from main, which prints one "<family>: N checks" line each.  GPU sanitizers are not available on the GPU pool, so this is where an
 // out-of-bounds LDS image / table index or a shift by the word size in fused_core.h / cg_core.h / plan_tables.h would show:
 // the prepared-order index map (prep_idx), the zeta-record LDS layout of basecase_each and the carry mask of gadget_digit included.
 // Built and run by tests/test_emu.py::test_kernel_bodies_under_address_and_ub_sanitizers (tests/emu/Makefile: sanitize).
@@ -7,6 +9,7 @@
 #include <cstdio>
 #include <cstring>
 #include <vector>
+#include "sanitize_cases.h"
 
 extern "C" {
 int emu_fused_poly_mult(uint32_t n, uint64_t q, uint64_t psi, int flags, const uint64_t* a, const uint64_t* b, uint64_t* c, size_t batch);
@@ -37,10 +40,9 @@ uint64_t lcg = 0x9E3779B97F4A7C15ull;
 uint64_t next() { lcg = lcg * 6364136223846793005ull + 1442695040888963407ull; return lcg; }
 uint64_t mulmod(uint64_t a, uint64_t b, uint64_t q) { return (uint64_t)(((unsigned __int128)a * b) % q); }
 uint64_t powmod(uint64_t b, uint64_t e, uint64_t q) { uint64_t r = 1; b %= q; while (e) { if (e & 1) r = mulmod(r, b, q); b = mulmod(b, b, q); e >>= 1; } return r; }
-int failures = 0, checks = 0;
 void expect(bool ok, const char* what, unsigned n, int a, int b, int c, int d) {
-  ++checks;
-  if (!ok) { ++failures; std::fprintf(stderr, "MISMATCH %s n=%u (%d %d %d %d)\n", what, n, a, b, c, d); }
+  ++tally.checks;
+  if (!ok) { ++tally.failures; std::fprintf(stderr, "MISMATCH %s n=%u (%d %d %d %d)\n", what, n, a, b, c, d); }
 }
 struct P { uint32_t n; uint64_t q, psi; };
 typedef std::vector<uint64_t> Rows;
@@ -176,6 +178,8 @@ void api_check_cases() {
 }
 }  // namespace
 
+Tally tally;
+
 int main() {
   // psi of the full-size sets squared down to smaller n (psi^(N/n) is a primitive 2n-th root)
   const P base24 = {4096, 8380417ull, 283817ull}, base60 = {4096, 1152921504606830593ull, 431606828070683274ull};
@@ -238,6 +242,18 @@ int main() {
   for (const P& p : sets)
     if ((p.n == 256) || (p.n == base60.n && p.q == base60.q)) family_cases(p);
   api_check_cases();
-  std::printf("sanitize_driver: %zu parameter sets, %d checks, %d failures\n", sets.size(), checks, failures);
-  return failures ? 1 : 0;
+  int counted = 0;
+  auto family = [&](const char* name, void (*cases)()) {
+    if (cases) cases();
+    std::printf("%s: %d checks\n", name, tally.checks - counted);
+    counted = tally.checks;
+  };
+  family("base", nullptr);                                                         // everything above
+  family("gadget2", gadget2_cases);
+  family("galois", galois_cases);
+  family("extprod", extprod_cases);
+  family("cmux", cmux_cases);
+  family("blindrot", blindrot_cases);
+  std::printf("sanitize_driver: %zu parameter sets, %d checks, %d failures\n", sets.size(), tally.checks, tally.failures);
+  return tally.failures ? 1 : 0;
 }

@@ -13,6 +13,14 @@ def load():
     return ctypes.CDLL(os.path.join(ROOT, "tests", "emu", "_build", "libemu.so"))
 
 
+def api_check(entry, *args):
+    """An *_api_check entry point of the library on args, whose last three parameters are (int* launch, char* msg, size_t msg_len)
+    -> (status, the text tn_last_error would give, the call goes on to a launch)."""
+    msg, launch = ctypes.create_string_buffer(256), ctypes.c_int(-1)
+    st = entry(*args, ctypes.byref(launch), msg, 256)
+    return st, msg.value.decode(), bool(launch.value)
+
+
 def smallest_dynamic_batch(row_bytes, resident, which=0):
     """The smallest batch that launch_plan.h's plan_rows hands out through the device counter for rows of row_bytes when
     `resident` workgroups are resident (which: 0 the fused kernels' policy, 1 the constant-geometry kernels'); one row fewer keeps

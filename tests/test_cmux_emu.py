@@ -1,18 +1,16 @@
-"""CPU stepping of the CMux rotation kernel (tests/emu_cmux/emu_cmux.cpp: polydot_cmux_kernel stepped thread by thread with the
+"""CPU stepping of the CMux rotation kernel (tests/emu/emu_cmux.cpp: polydot_cmux_kernel stepped thread by thread with the
 kernel's own headers: the masked exponent, rotated-minus-own words, one forward transform per term, two inverses, the add-in)
 against a numpy statement of the definition (the monomial product in numpy, the stepping of the external-product kernel, the
 addition mod q), against the oracle's products of the Python-decomposed digits, against an algebraic identity that does not
 pass through the project's decomposition, and the two entry points' argument lists (csrc/api_checks.h: check_monomial,
 check_cmux_rotate), without a GPU."""
 import ctypes
-import functools
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, P64, _make, p64
+import emu_library
+from conftest import P64, p64
 from test_dot_emu import sum_mod
 from test_extprod_emu import EmuExtprod, digit_rows, ext_rows, input_rows
 from test_gadget_emu import MODES, POLICIES, gadget_pairs
@@ -47,18 +45,11 @@ def monomial_np(a, exps, q, minus_one=False):
     return out
 
 
-@functools.lru_cache(maxsize=None)
-def load():
-    """make -C tests/emu_cmux (nothing to do when the library is newer than its sources), then the ctypes handle."""
-    _make("tests/emu_cmux")
-    return ctypes.CDLL(os.path.join(ROOT, "tests", "emu_cmux", "_build", "libemu_cmux.so"))
-
-
 class EmuCmux:
-    """The entry points of tests/emu_cmux/_build/libemu_cmux.so."""
+    """The entry points of tests/emu/emu_cmux.cpp in tests/emu/_build/libemu.so."""
 
     def __init__(self):
-        L = self.lib = load()
+        L = self.lib = emu_library.load()
         vp, u32, u64, sz, ci = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_size_t, ctypes.c_int
         L.emu_poly_cmux_rotate_prepared.argtypes = [u32, u64, u64, ci, P64, P32, P64, sz, P64, sz, sz, u32, u32]
         L.emu_monomial_mul.argtypes = [u32, u64, P64, P32, P64, sz, sz, u32]
@@ -93,14 +84,10 @@ class EmuCmux:
 
     def check(self, view, a, e, b, c, sets=1, batch=1, comps=2, terms=1, base_log=1, flags=0):
         """check_cmux_rotate on the plan view (n, elem_bytes, has_fused, omega_only, q) -> (status, text, goes on to a launch)."""
-        msg, launch = ctypes.create_string_buffer(256), ctypes.c_int(-1)
-        st = self.lib.emu_cmux_api_check(*view, a, e, b, c, sets, batch, comps, terms, base_log, flags, ctypes.byref(launch), msg, 256)
-        return st, msg.value.decode(), bool(launch.value)
+        return emu_library.api_check(self.lib.emu_cmux_api_check, *view, a, e, b, c, sets, batch, comps, terms, base_log, flags)
 
     def check_monomial(self, view, a, e, out, batch=1, group=1, flags=0):
-        msg, launch = ctypes.create_string_buffer(256), ctypes.c_int(-1)
-        st = self.lib.emu_monomial_api_check(*view, a, e, out, batch, group, flags, ctypes.byref(launch), msg, 256)
-        return st, msg.value.decode(), bool(launch.value)
+        return emu_library.api_check(self.lib.emu_monomial_api_check, *view, a, e, out, batch, group, flags)
 
 
 @pytest.fixture(scope="module")
@@ -338,18 +325,3 @@ def test_argument_list_of_the_monomial_call(cmux, row):
     st, got, goes_on = cmux.check_monomial(view, a, e, out, **full)
     assert (st, goes_on) == (status, launches), (st, got, goes_on)
     assert got == (text or ""), got
-
-
-def test_stepping_under_address_and_ub_sanitizers():
-    """The same source with its own main under AddressSanitizer + UBSan, built and run once as a stand-alone program (nothing is
-    loaded into Python): the stepping at n = 256 with 32-bit and 64-bit lanes and at the base-case shape, both policies, the
-    exponents 0, 1, n, 2n - 1 and an unreduced one, the monomial product, and both argument lists on made-up addresses."""
-    d = os.path.join(ROOT, "tests", "emu_cmux")
-    b = subprocess.run(["make", "-C", d, "_build/sanitize_cmux"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert b.returncode == 0, b.stdout[-2000:]
-    r = subprocess.run([os.path.join(d, "_build", "sanitize_cmux")], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
-                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1"))
-    assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
-    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-3000:]
-    m = __import__("re").search(r"(\d+) checks, 0 failures", r.stdout)
-    assert m and int(m.group(1)) >= 400, r.stdout

@@ -351,17 +351,39 @@ def test_kernel_bodies_under_address_and_ub_sanitizers():
     64-bit lanes and at the base-case shape, both policies, batch 2 x 2 terms, one shared prepared set and one per row; and the
     entry points' argument checks (csrc/api_checks.h) on made-up addresses: overlap against byte-by-byte intersection next to
     address 0, the row limit at its boundary and at (3, 2^63): 209 checks.  The driver
-    also cross-checks every result (tests/emu/sanitize_driver.cpp).  It is a stand-alone program: nothing is loaded into Python."""
+    also cross-checks every result (tests/emu/sanitize_driver.cpp).  It is a stand-alone program: nothing is loaded into Python.
+
+    The five later families run in the same program, each from the cases next to its stepping (tests/emu/emu_<family>.cpp), and
+    the driver prints one "<family>: N checks" line each.  Each steps its kernel at n = 256 with 32-bit and 64-bit lanes and at
+    the base-case shape (n = 4096, 60-bit), both policies, and runs its argument list on made-up addresses, overlap against the
+    byte-by-byte intersection:
+      gadget2   batch 2 x 2 terms, one shared set and one per row, both digit modes, each component against the one-component stepping;
+      galois    both kernels over every tile shape and lane width, the prepared kernel on every fused n = 256 .. 8192 at both lane
+                widths with both policies and the base case, on an LDS image of exactly the launcher's size.  For the prepared
+                kernel it is a memory-safety run (its words are checked in tests/test_galois_emu.py);
+      extprod   ins 2 and 3, against the sum over the inputs taken one at a time;
+      cmux      the exponents 0, 1, n, 2n - 1 and an unreduced one, the monomial product, both argument lists;
+      blindrot  three steps in place and out of place against three calls of one step, the hazard tags, the LDS rule."""
+    import re
     import subprocess
+    from conftest import ntt_prime_below
+    Q23, Q60 = 8380417, 1152921504606830593          # the reference's two moduli
     d = os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu")
     b = subprocess.run(["make", "-j8", "-C", d, "sanitize"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     assert b.returncode == 0, b.stdout[-2000:]
     r = subprocess.run([os.path.join(d, "_build", "sanitize_driver")], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
                        env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1"))
+    print(r.stdout[-1500:])
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
     assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-3000:]
-    m = __import__("re").search(r"(\d+) checks, 0 failures", r.stdout)
-    assert m and int(m.group(1)) > 2859, r.stdout
+    floors = {"base": 2890, "gadget2": 360, "galois": 1182, "extprod": 525, "cmux": 420, "blindrot": 496}
+    counts = {name: int(v) for name, v in re.findall(r"^(\w+): (\d+) checks$", r.stdout, re.M)}
+    assert sorted(counts) == sorted(floors) and all(counts[f] >= floors[f] for f in floors), r.stdout
+    m = re.search(r"(\d+) checks, 0 failures", r.stdout)
+    assert m and int(m.group(1)) == sum(counts.values()), r.stdout
+    for n in (256, 512, 1024, 2048, 4096, 8192):                              # galois: every fused n, the 64 KiB image of n = 8192 included
+        for q in (Q60, Q23 if n <= 4096 else ntt_prime_below(2 ** 31, 8192)):
+            assert f"prepared n={n} q={q} both policies: ok" in r.stdout, (n, q, r.stdout)
 
 
 @pytest.mark.parametrize("n,q", __import__("chosen_rows").SHAPES)

@@ -1,16 +1,14 @@
-"""CPU stepping of the external-product kernel (tests/emu_extprod/emu_extprod.cpp: polydot_extprod_kernel stepped thread by
+"""CPU stepping of the external-product kernel (tests/emu/emu_extprod.cpp: polydot_extprod_kernel stepped thread by
 thread with the kernel's own headers: two sums over ins * terms terms, one forward transform per term, two inverses) against
 the stepping of the one-component dot kernel on the concatenated Python-decomposed digits, against the oracle's products of
 those digits, and the new entry point's argument list (csrc/api_checks.h: check_external_product), without a GPU."""
 import ctypes
-import functools
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, P64, _make, p64
+import emu_library
+from conftest import P64, p64
 from test_dot_emu import EmuDot, sum_mod
 from test_gadget2_emu import EmuGadget2
 from test_gadget_emu import MODES, POLICIES, decompose_rows, gadget_pairs
@@ -21,18 +19,11 @@ FN = "tn_poly_external_product_prepared_dev"
 INS = (2, 3)
 
 
-@functools.lru_cache(maxsize=None)
-def load():
-    """make -C tests/emu_extprod (nothing to do when the library is newer than its sources), then the ctypes handle."""
-    _make("tests/emu_extprod")
-    return ctypes.CDLL(os.path.join(ROOT, "tests", "emu_extprod", "_build", "libemu_extprod.so"))
-
-
 class EmuExtprod:
-    """The entry points of tests/emu_extprod/_build/libemu_extprod.so."""
+    """The entry points of tests/emu/emu_extprod.cpp in tests/emu/_build/libemu.so."""
 
     def __init__(self):
-        L = self.lib = load()
+        L = self.lib = emu_library.load()
         vp, u32, u64, sz, ci = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_size_t, ctypes.c_int
         L.emu_poly_external_product_prepared.argtypes = [u32, u64, u64, ci, P64, P64, sz, P64, sz, sz, sz, u32, u32]
         L.emu_extprod_api_check.argtypes = [u32, ci, ci, ci, u64, vp, vp, vp, sz, sz, sz, sz, sz, u32, u32, ctypes.POINTER(ci), ctypes.c_char_p, sz]
@@ -51,9 +42,7 @@ class EmuExtprod:
 
     def check(self, view, a, b, c, sets=1, batch=1, ins=2, outs=2, terms=1, base_log=1, flags=0):
         """check_external_product on the plan view (n, elem_bytes, has_fused, omega_only, q) -> (status, text, goes on to a launch)."""
-        msg, launch = ctypes.create_string_buffer(256), ctypes.c_int(-1)
-        st = self.lib.emu_extprod_api_check(*view, a, b, c, sets, batch, ins, outs, terms, base_log, flags, ctypes.byref(launch), msg, 256)
-        return st, msg.value.decode(), bool(launch.value)
+        return emu_library.api_check(self.lib.emu_extprod_api_check, *view, a, b, c, sets, batch, ins, outs, terms, base_log, flags)
 
 
 @pytest.fixture(scope="module")
@@ -268,18 +257,3 @@ def test_one_input_has_the_multidot_calls_answers(extprod, gadget2):
         st, got, goes_on = extprod.check(view, a, b, c, ins=1, **full)
         assert (st, goes_on) == (status, launches), row[0]
         assert got == (text or "").replace(g2.FN, FN).replace("batch * outs * terms", "batch * outs * ins * terms"), row[0]
-
-
-def test_stepping_under_address_and_ub_sanitizers():
-    """The same source with its own main under AddressSanitizer + UBSan, built and run once as a stand-alone program (nothing is
-    loaded into Python): the stepping at n = 256 with 32-bit and 64-bit lanes and at the base-case shape, both policies, ins 2
-    and 3, and the argument list on made-up addresses, overlap against the byte-by-byte intersection."""
-    d = os.path.join(ROOT, "tests", "emu_extprod")
-    b = subprocess.run(["make", "-C", d, "sanitize"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert b.returncode == 0, b.stdout[-2000:]
-    r = subprocess.run([os.path.join(d, "_build", "sanitize_extprod")], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
-                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1"))
-    assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
-    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-3000:]
-    m = __import__("re").search(r"(\d+) checks, 0 failures", r.stdout)
-    assert m and int(m.group(1)) >= 500, r.stdout

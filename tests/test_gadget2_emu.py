@@ -1,16 +1,14 @@
-"""CPU stepping of the two-component gadget kernel (tests/emu_gadget2/emu_gadget2.cpp: polydot_gadget2_kernel stepped thread by
+"""CPU stepping of the two-component gadget kernel (tests/emu/emu_gadget2.cpp: polydot_gadget2_kernel stepped thread by
 thread with the kernel's own headers: one forward transform per term, two products, two sums, two inverses) against the
 stepping of the one-component kernel on the matching slices of the prepared operand, against the oracle's products of the
 Python-decomposed digits, and the new entry point's argument list (csrc/api_checks.h: check_gadget_multidot), without a GPU."""
 import ctypes
-import functools
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, P64, _make, p64
+import emu_library
+from conftest import P64, p64
 from test_dot_emu import sum_mod
 from test_gadget_emu import MODES, POLICIES, EmuGadget, decompose_rows, gadget_pairs
 from test_prepared_emu import CASES, CASE_IDS, EmuPrepared, _case_data
@@ -19,18 +17,11 @@ OK, EINVAL, EUNSUPPORTED = 0, 6, 7
 FN = "tn_poly_gadget_multidot_prepared_dev"
 
 
-@functools.lru_cache(maxsize=None)
-def load():
-    """make -C tests/emu_gadget2 (nothing to do when the library is newer than its sources), then the ctypes handle."""
-    _make("tests/emu_gadget2")
-    return ctypes.CDLL(os.path.join(ROOT, "tests", "emu_gadget2", "_build", "libemu_gadget2.so"))
-
-
 class EmuGadget2:
-    """The entry points of tests/emu_gadget2/_build/libemu_gadget2.so."""
+    """The entry points of tests/emu/emu_gadget2.cpp in tests/emu/_build/libemu.so."""
 
     def __init__(self):
-        L = self.lib = load()
+        L = self.lib = emu_library.load()
         vp, u32, u64, sz, ci = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_size_t, ctypes.c_int
         L.emu_poly_gadget_multidot_prepared.argtypes = [u32, u64, u64, ci, P64, P64, sz, P64, sz, sz, sz, u32, u32]
         L.emu_gadget2_api_check.argtypes = [u32, ci, ci, ci, u64, vp, vp, vp, sz, sz, sz, sz, u32, u32, ctypes.POINTER(ci), ctypes.c_char_p, sz]
@@ -49,9 +40,7 @@ class EmuGadget2:
 
     def check(self, view, a, b, c, sets=1, batch=1, outs=2, terms=1, base_log=1, flags=0):
         """check_gadget_multidot on the plan view (n, elem_bytes, has_fused, omega_only, q) -> (status, text, goes on to a launch)."""
-        msg, launch = ctypes.create_string_buffer(256), ctypes.c_int(-1)
-        st = self.lib.emu_gadget2_api_check(*view, a, b, c, sets, batch, outs, terms, base_log, flags, ctypes.byref(launch), msg, 256)
-        return st, msg.value.decode(), bool(launch.value)
+        return emu_library.api_check(self.lib.emu_gadget2_api_check, *view, a, b, c, sets, batch, outs, terms, base_log, flags)
 
 
 @pytest.fixture(scope="module")
@@ -178,7 +167,6 @@ def test_argument_list(gadget2, row):
 def test_one_component_has_the_gadget_calls_answers(gadget2):
     """outs == 1: status and launch of every row of the gadget call's own table (tests/api_cases.py), texts but for the name."""
     import api_cases
-    import emu_library
     lib = emu_library.load()
     n, word, q = 256, 4, 8380417
     seen = 0
@@ -195,18 +183,3 @@ def test_one_component_has_the_gadget_calls_answers(gadget2):
         assert text2 == text.replace("tn_poly_gadget_dot_prepared_dev", FN).replace("batch * terms", "batch * outs * terms"), case.id
         seen += 1
     assert seen > 30
-
-
-def test_stepping_under_address_and_ub_sanitizers():
-    """The same source with its own main under AddressSanitizer + UBSan, built and run once as a stand-alone program (nothing is
-    loaded into Python): the stepping at n = 256 with 32-bit and 64-bit lanes and at the base-case shape, both policies, and the
-    argument list on made-up addresses, overlap against the byte-by-byte intersection."""
-    d = os.path.join(ROOT, "tests", "emu_gadget2")
-    b = subprocess.run(["make", "-C", d, "sanitize"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert b.returncode == 0, b.stdout[-2000:]
-    r = subprocess.run([os.path.join(d, "_build", "sanitize_gadget2")], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
-                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1"))
-    assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
-    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-3000:]
-    m = __import__("re").search(r"(\d+) checks, 0 failures", r.stdout)
-    assert m and int(m.group(1)) >= 300, r.stdout

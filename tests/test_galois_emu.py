@@ -1,16 +1,15 @@
-"""CPU stepping of the automorphism kernels (tests/emu_galois/emu_galois.cpp: automorphism_kernel and automorphism_hat_kernel
+"""CPU stepping of the automorphism kernels (tests/emu/emu_galois.cpp: automorphism_kernel and automorphism_hat_kernel
 stepped tile by tile with the header the gfx950 kernels are compiled from, csrc/galois_core.h) against sigma_g written from its
 definition (include/tinyntt.h) in numpy below, the index maps' properties, the LDS bank model of the gathers, the argument list of
 both entry points (csrc/api_checks.h: check_automorphism) and numtheory.galois_element, without a GPU."""
 import ctypes
 import functools
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, P64, PARAMS, _make, ntt_prime_below, p64
+import emu_library
+from conftest import P64, PARAMS, ntt_prime_below, p64
 from test_hat_emu import EmuHat
 from test_prepared_emu import Q23, Q60, EmuPrepared, shape_params
 from tiny_ntt_amd import numtheory
@@ -46,22 +45,15 @@ def seeded_elements(n, count, seed):
 
 
 # ---- the library ------------------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def load():
-    """make -C tests/emu_galois (nothing to do when the library is newer than its sources), then the ctypes handle."""
-    _make("tests/emu_galois")
-    return ctypes.CDLL(os.path.join(ROOT, "tests", "emu_galois", "_build", "libemu_galois.so"))
-
-
 def u32s(values):
     return (ctypes.c_uint32 * max(len(values), 1))(*values)
 
 
 class EmuGalois:
-    """The entry points of tests/emu_galois/_build/libemu_galois.so."""
+    """The entry points of tests/emu/emu_galois.cpp in tests/emu/_build/libemu.so."""
 
     def __init__(self):
-        L = self.lib = load()
+        L = self.lib = emu_library.load()
         vp, u32, u64, sz, ci = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_size_t, ctypes.c_int
         L.emu_automorphism.argtypes = [u32, u64, P64, P64, sz, P32, sz]
         L.emu_automorphism_prepared.argtypes = [u32, u64, u64, ci, P64, P64, sz, P32, sz, ctypes.POINTER(ci)]
@@ -102,11 +94,9 @@ class EmuGalois:
 
     def check(self, view, prepared, a, out, batch, galois, count=None):
         """check_automorphism on the plan view (n, elem_bytes, has_fused, omega_only, q) -> (status, text, goes on to a launch)."""
-        msg, launch = ctypes.create_string_buffer(256), ctypes.c_int(-1)
         g = None if galois is None else u32s(galois)
         count = len(galois) if count is None else count
-        st = self.lib.emu_galois_api_check(*view, int(prepared), a, out, batch, g, count, ctypes.byref(launch), msg, 256)
-        return st, msg.value.decode(), bool(launch.value)
+        return emu_library.api_check(self.lib.emu_galois_api_check, *view, int(prepared), a, out, batch, g, count)
 
 
 @pytest.fixture(scope="module")
@@ -446,23 +436,3 @@ def test_galois_element(n):
         assert g % 2 == 1 and gi % 2 == 1 and 1 <= g < m and 1 <= gi < m
         c = numtheory.galois_element(n, step, conjugate=True)
         assert c == g * (m - 1) % m and c % 2 == 1
-
-
-# ---- the sanitizers ----------------------------------------------------------------------------------------------------
-def test_stepping_under_address_and_ub_sanitizers():
-    """The same source with its own main under AddressSanitizer + UBSan, built and run once as a stand-alone program (nothing is
-    loaded into Python): both kernels over every tile shape and lane width, the prepared kernel on every fused n = 256 .. 8192
-    at both lane widths with both policies and the base case, on an LDS image of exactly the launcher's size; the argument list
-    on made-up addresses.  For the prepared kernel it is a memory-safety run (its words are checked above)."""
-    d = os.path.join(ROOT, "tests", "emu_galois")
-    b = subprocess.run(["make", "-C", d, "sanitize"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert b.returncode == 0, b.stdout[-2000:]
-    r = subprocess.run([os.path.join(d, "_build", "sanitize_galois")], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
-                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1"))
-    assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
-    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-3000:]
-    m = __import__("re").search(r"(\d+) checks, 0 failures", r.stdout)
-    assert m and int(m.group(1)) >= 1100, r.stdout
-    for n in (256, 512, 1024, 2048, 4096, 8192):                              # every fused n, the 64 KiB image of n = 8192 included
-        for q in (Q60, Q23 if n <= 4096 else ntt_prime_below(2 ** 31, 8192)):
-            assert f"prepared n={n} q={q} both policies: ok" in r.stdout, (n, q, r.stdout)

@@ -1,7 +1,7 @@
 """GPU tests of tn_poly_blind_rotate_prepared_dev (Plan.poly_blind_rotate_prepared): a blind rotation from one launch with the
 accumulator in LDS across the steps, bit for bit against the loop it replaces on the device (Plan.blind_rotate: one
 tn_poly_cmux_rotate_prepared_dev launch per step over two alternating buffers), against the CPU stepping of the kernel
-(tests/emu_blindrot) and against an algebraic identity that does not pass through the project's decomposition."""
+(tests/emu/emu_blindrot.cpp) and against an algebraic identity that does not pass through the project's decomposition."""
 
 import ctypes
 

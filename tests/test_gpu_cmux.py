@@ -1,7 +1,7 @@
 """GPU tests of tn_monomial_mul_dev and tn_poly_cmux_rotate_prepared_dev (Plan.monomial_mul, Plan.poly_cmux_rotate_prepared,
 Plan.blind_rotate): one step of a blind rotation from one launch, bit for bit against the explicit route on the device
 (tn_monomial_mul_dev with TN_MONOMIAL_MINUS_ONE, tn_poly_external_product_prepared_dev, the addition mod q) and against the CPU
-stepping of the kernel (tests/emu_cmux); the monomial product against the numpy statement of its definition."""
+stepping of the kernel (tests/emu/emu_cmux.cpp); the monomial product against the numpy statement of its definition."""
 
 import ctypes
 

@@ -1,6 +1,6 @@
 """GPU tests of tn_poly_external_product_prepared_dev (Plan.poly_external_product_prepared): the external product RGSW x RLWE from
 one launch, bit for bit against route B on the device (tn_gadget_decompose_dev on the batch * ins rows, then
-tn_poly_dot_prepared_dev with ins * terms terms per component) and against the CPU stepping of the kernel (tests/emu_extprod)."""
+tn_poly_dot_prepared_dev with ins * terms terms per component) and against the CPU stepping of the kernel (tests/emu/emu_extprod.cpp)."""
 
 import ctypes
 

@@ -1,6 +1,6 @@
 """GPU tests of tn_poly_gadget_multidot_prepared_dev (Plan.poly_gadget_multidot_prepared): both components of a key switch from
 one launch, bit for bit against tn_poly_gadget_dot_prepared_dev per component and against the CPU stepping of the
-two-component kernel (tests/emu_gadget2)."""
+two-component kernel (tests/emu/emu_gadget2.cpp)."""
 
 import ctypes
 

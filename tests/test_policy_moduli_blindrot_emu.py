@@ -1,8 +1,8 @@
-"""CPU stepping of the blind-rotation kernel (tests/emu_blindrot) at the policy-boundary moduli of tests/policy_moduli.py, the
+"""CPU stepping of the blind-rotation kernel (tests/emu/emu_blindrot.cpp) at the policy-boundary moduli of tests/policy_moduli.py, the
 full table: the last prime each bound schedule accepts and the first it refuses, among them the last modulus the base case
 accepts and the first it refuses at n = 4096; lazy plans and, where lazy, forced-canonical plans.  Batch 7, two steps (step 0
 with the exponents of tests/test_cmux_emu.py), every (terms, w) of gadget_pairs with the digit modes alternating over the
-pairs: against the loop of stepped CMux rotations (tests/emu_cmux) on the steps' shared keys.  A shape the LDS rule refuses is
+pairs: against the loop of stepped CMux rotations (tests/emu/emu_cmux.cpp) on the steps' shared keys.  A shape the LDS rule refuses is
 refused by the stepping."""
 import numpy as np
 import pytest

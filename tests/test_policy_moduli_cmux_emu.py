@@ -1,4 +1,4 @@
-"""CPU stepping of the CMux rotation kernel (tests/emu_cmux) at the policy-boundary moduli of tests/policy_moduli.py, the full
+"""CPU stepping of the CMux rotation kernel (tests/emu/emu_cmux.cpp) at the policy-boundary moduli of tests/policy_moduli.py, the full
 table: the last prime each bound schedule accepts and the first it refuses, among them the last modulus the base case accepts
 and the first it refuses at n = 4096; lazy plans and, where lazy, forced-canonical plans.  Batch 7 with the exponents of
 tests/test_cmux_emu.py, every (terms, w) of gadget_pairs: against the numpy statement of the definition (the monomial in

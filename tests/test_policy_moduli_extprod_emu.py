@@ -1,4 +1,4 @@
-"""CPU stepping of the external-product kernel (tests/emu_extprod) at the policy-boundary moduli of tests/policy_moduli.py, the
+"""CPU stepping of the external-product kernel (tests/emu/emu_extprod.cpp) at the policy-boundary moduli of tests/policy_moduli.py, the
 full table: the last prime each bound schedule accepts and the first it refuses, among them the last modulus the base case
 accepts and the first it refuses at n = 4096; lazy plans and, where lazy, forced-canonical plans.  ins = 2, batch 5, every
 (terms, w) of gadget_pairs: against the oracle's summed products of the Python-decomposed digits and against route B (the
