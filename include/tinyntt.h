@@ -535,6 +535,66 @@ tn_status tn_automorphism_prepared_dev(tn_plan *plan, const void *xhat, void *ou
                                        void *stream);
 
 /*
+ * AUTOMORPHISM KEY SWITCH: the homomorphic automorphism of an RLWE ciphertext (c0, c1) under a key from sigma_g(s) to s,
+ *     out0 = sigma_g(c0) + sum_j digit_j(sigma_g(c1)) * K[0][j]
+ *     out1 =               sum_j digit_j(sigma_g(c1)) * K[1][j],
+ * from ONE launch (tn_poly_galois_keyswitch_prepared_dev): the rotation of BFV / CKKS-style schemes, one step of a trace or of
+ * LWE -> RLWE packing, the step between external products of an automorphism-based blind rotation (LMKCDEY).  sigma_g is a
+ * signed index map on the load the gadget kernel performs anyway and sigma_g(c0) an add-in at its store; no transform is added:
+ * terms + 2 per row, as in tn_poly_gadget_multidot_prepared_dev with outs = 2.
+ *
+ * tn_poly_galois_keyswitch_prepared_dev:
+ *     c[r][o] = ( [o == 0] sigma_g(a[r][0]) + sum_{j < terms} digit_j( sigma_g(a[r][1]) ) * b[s][o][j] ) mod q,
+ * o < 2, s = (bhat_sets == 1 ? 0 : r), r < batch.  a is [batch][2][n], any word values, taken mod q: a[r][0] is only rotated,
+ * a[r][1] is rotated and switched.  bhat is [bhat_sets][2][terms][n] prepared rows, exactly the layout of
+ * tn_poly_gadget_multidot_prepared_dev with outs = 2; bhat_sets is 1 (one key for every row) or batch.  c is [batch][2][n],
+ * canonical residues.  sigma_g is the map defined above (GALOIS AUTOMORPHISMS); galois is ONE odd element below 2n, passed by
+ * value: no table, nothing is set up per g, and a captured launch replays the g it was captured with.  Digits, base_log and
+ * flags (TN_GADGET_BALANCED) are the gadget calls'.
+ * The result is BIT-IDENTICAL to the explicit route on the same buffers: tn_automorphism_dev on a viewed as batch * 2 rows with
+ * count = 1; tn_poly_gadget_multidot_prepared_dev with outs = 2 on the rotated a[r][1] rows; component 0 plus the rotated
+ * a[r][0], word-wise mod q.  sigma_g is applied BEFORE the digits are cut, and that order is part of the contract: a balanced
+ * digit of q - x is not minus the digit of x, so rotating the digits of a[r][1] instead is a different function of the inputs.
+ * g = 1 is a plain key switch with its body added in, c = (a0 + <digits(a1), K[0]>, <digits(a1), K[1]>), useful by itself.
+ * c must not overlap a or bhat (byte ranges): the kernel permutes within a row and prefetches the next one, so the call does
+ * not run in place.  The index into the row is masked: no value of galois could cause an out-of-bounds access.
+ *
+ * When to use which (MI355X, profiles/galoisks_ab.txt, tools/gpu_galoisks.py; balanced digits, terms 2 - 4, g in {3, 5, 2n - 1,
+ * one seeded} reported as a range, shared key and key per row, 9 interleaved repeats; a point counts as faster only where the
+ * one launch's slowest repeat is below the other's fastest; all outputs compared in full first):
+ *   - the homomorphic automorphism of a batch of ciphertexts: tn_poly_galois_keyswitch_prepared_dev is faster than the explicit
+ *     route (tn_automorphism_dev, tn_poly_gadget_multidot_prepared_dev, the addition in torch) at all twelve measured points, for
+ *     every g, by disjoint ranges: x 0.50 - 0.63 at n = 4096 / 60-bit, 65,536 rows (4,608 - 4,729 against 9,309 - 9,321 us at two
+ *     terms, shared key) and x 0.51 - 0.63 at n = 1024 / 24-bit, 4,096 rows (44.5 - 44.6 against 87.9 - 88.0 us).  The gain shrinks
+ *     with terms: the saving is a fixed amount per row.  The route was timed on the layout that suits it, [2][batch][n], where
+ *     the rotated second components are contiguous rows; a caller who holds [batch][2][n] pays a copy on top of it.
+ *   - against the route's two library launches WITHOUT the addition it is still faster at all twelve points by disjoint ranges,
+ *     x 0.77 - 0.88 at n = 4096 and x 0.82 - 0.90 at n = 1024: a caller with a fused addition of their own gains that much.
+ *   - against a plain tn_poly_gadget_multidot_prepared_dev launch (outs = 2) on the unrotated second components it is SLOWER at
+ *     all twelve points, for every g, by disjoint ranges: x 1.06 - 1.14 at n = 4096 (390 - 810 us more for 65,536 rows) and
+ *     x 1.06 - 1.11 at n = 1024 (3 - 6 us more for 4,096 rows): the price of the two permutations, their barriers and the second
+ *     input row.  g = 3 is the slowest element at n = 4096 with a shared key (4,729 against 4,608 - 4,619 us at two terms, 7,295
+ *     against 6,976 - 6,997 us at four) and at n = 1024 with a key per row (71.6 against 70.0 us at four terms); elsewhere the
+ *     elements are within 1.3 % of one another.  Why was not isolated.
+ *   - g = 1, a key switch with its body added in: not timed by itself; it runs the same code as every other g.
+ *   - not measured: n = 256, n = 8192, the canonical policy, unsigned digits.
+ *
+ * Out of scope: a c = a + ... flag for trace steps; several g per call with one key each; a Galois element per row; rank above
+ * 1; and the hoisted form (decompose once, rotate the transformed digits with tn_automorphism_prepared_dev), which is a
+ * different function of its inputs and not bit-identical to this one.
+ *
+ * Status, in this order: TN_EINVAL for a NULL plan; TN_EUNSUPPORTED for a plan without the fused kernels; TN_EINVAL for a galois
+ * that is even or >= 2n (the text names it); for everything the gadget calls refuse (terms == 0, a flag bit other than
+ * TN_GADGET_BALANCED, base_log == 0 or 2^base_log >= q, (terms - 1) * base_log >= 64, batch * 2 * terms > 2^31 - 1); batch == 0
+ * succeeds and launches nothing; TN_EINVAL for a NULL buffer, for bhat_sets neither 1 nor batch, and for c's batch * 2 rows
+ * overlapping a's batch * 2 rows or bhat's bhat_sets * 2 * terms rows.
+ * The call enqueues on the stream and returns, and may be stream-captured (a captured launch hands rows out at the fixed
+ * stride).  Fused plans only; no cyclic variant, no *_host form and no tn_multi_* form.  The reference has no counterpart.
+ */
+tn_status tn_poly_galois_keyswitch_prepared_dev(tn_plan *plan, const void *a, uint32_t galois, const void *bhat, size_t bhat_sets,
+                                                void *c, size_t batch, size_t terms, uint32_t base_log, uint32_t flags, void *stream);
+
+/*
  * The *_host entry points cut the batch into chunks that flow H2D -> kernel -> D2H on three
  * streams through a fixed set of device staging slots (copies overlap the kernels when the host
  * buffers are pinned; device staging stays bounded whatever the batch).  rows = rows per chunk,

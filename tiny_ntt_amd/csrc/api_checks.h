@@ -211,6 +211,15 @@ static inline bool check_automorphism(ApiCheck& k, const void* in, const void* o
   return k.plan() && (!prepared || k.fused()) && k.galois(galois, count) && k.rows(batch, count, "batch * count", "output rows") &&
          k.work(batch) && k.buffers(in && out && galois) && k.apart(out, batch * count, in, batch, "the input");
 }
+// tn_poly_galois_keyswitch_prepared_dev: check_gadget_multidot's list with two components and the Galois element (one, by
+// value) behind the plan's steps: the row limit holds for batch * 2 * terms, a and c have batch * 2 rows and bhat
+// sets * 2 * terms.  The kernel permutes within a row and prefetches the next one, so nothing runs in place.
+static inline bool check_galois_keyswitch(ApiCheck& k, const void* a, uint32_t galois, const void* bhat, size_t sets, const void* c, size_t batch,
+                                          size_t terms, uint32_t base_log, uint32_t flags) {
+  return k.plan() && k.fused() && k.galois(&galois, 1) && k.gadget(rows_times(batch, 2), terms, base_log, flags, "batch * 2 * terms") &&
+         k.work(batch) && k.buffers(a && bhat && c) && k.sets(sets, batch, "bhat_sets", "one set of operands for every row") &&
+         k.apart(c, batch * 2, a, batch * 2, "an input") && k.apart(c, batch * 2, bhat, sets * 2 * terms, "an input");
+}
 static inline bool check_pointwise(ApiCheck& k, const void* a, const void* b, const void* c, size_t batch) {      // in place is allowed
   return k.plan() && k.rows_wide(batch) && k.buffers(!batch || (a && b && c));
 }

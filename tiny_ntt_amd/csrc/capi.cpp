@@ -309,6 +309,15 @@ extern "C" tn_status tn_poly_cmux_rotate_prepared_dev(tn_plan* p, const void* a,
   return TN_OK;
 }
 
+// ---- automorphism key switch: sigma_g of both components, the key switch of the second, the first added in, one launch ------
+extern "C" tn_status tn_poly_galois_keyswitch_prepared_dev(tn_plan* p, const void* a, uint32_t galois, const void* bhat, size_t bhat_sets, void* c,
+                                                           size_t batch, size_t terms, uint32_t base_log, uint32_t flags, void* stream) {
+  TN_CHECK("tn_poly_galois_keyswitch_prepared_dev", check_galois_keyswitch(k, a, galois, bhat, bhat_sets, c, batch, terms, base_log, flags));
+  TN_ON_DEVICE(p);
+  TN_HIP(launch_polydot_galoisks(p, a, galois, bhat, bhat_sets == 1, c, batch, terms, base_log, (flags & TN_GADGET_BALANCED) != 0, pick_stream(p, stream)));
+  return TN_OK;
+}
+
 // ---- blind rotation: `steps` CMux rotation steps from one launch, the accumulator in LDS across them ------------------------
 extern "C" tn_status tn_poly_blind_rotate_prepared_dev(tn_plan* p, const void* a, const uint32_t* exps, const void* bhat, void* c, size_t batch,
                                                        size_t comps, size_t steps, size_t terms, uint32_t base_log, uint32_t flags, void* stream) {

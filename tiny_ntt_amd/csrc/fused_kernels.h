@@ -8,6 +8,8 @@
 //   kernels_gadget.hip    gadget decomposition and the dot product that decomposes a itself
 //   kernels_extprod.hip   external product: the digits of all input polynomials of a row into both output components
 //   kernels_cmux.hip      CMux rotation step: the external product of (X^e - 1) * a, added to a
+//   kernels_blindrot.hip  blind rotation: CMux rotation steps with the accumulator kept in LDS
+//   kernels_galoisks.hip  automorphism key switch: sigma_g on the load, the two-component gadget product, the add-in at the store
 #pragma once
 #include <hip/hip_runtime.h>
 #include <type_traits>

@@ -1,6 +1,8 @@
 // galois_core.h — the ring automorphism sigma_g : a(x) -> a(x^g) mod (x^n + 1), g odd, on coefficient rows and on prepared
-// rows: the index maps and the per-thread code of the two kernels of kernels_galois.hip, free of HIP, so tests/emu_galois
+// rows: the index maps and the per-thread code of the two kernels of kernels_galois.hip, free of HIP, so tests/emu
 // steps on the CPU exactly what the gfx950 kernels run.  include/tinyntt.h has the definition; DESIGN.md 3.2f the derivation.
+// Also the per-word code of the automorphism key switch (kernels_galoisks.hip): galois_dst, galois_scatter_word,
+// galois_add_in.
 //
 // Both kernels take a tile of rows through an LDS image: every thread stages words at unit stride (galois_stage), one barrier,
 // then for each of the call's elements every thread reads the sources of its destination words from the image and stores them
@@ -87,6 +89,22 @@ template <typename E> TN_HD void galois_st(E* p, E v) {
 }
 
 template <typename E> TN_HD E galois_neg(E x, E q) { return x ? (E)(q - x) : (E)0; }      // -x mod q for canonical x; 0 stays 0
+
+// Coefficients, scatter form (polydot_galoisks_kernel, kernels_galoisks.hip: the holder of a source word puts it where sigma_g
+// takes it): source word s goes to word (s g) mod n, negated where bit log2 n of s g mod 2n is set (s g < 2^27).  The index
+// is MASKED to the row: no g addresses a word outside it.  The same map as galois_src, read from the other side.
+TN_HD u32 galois_dst(u32 s, u32 g, u32 logn, bool& negate) {
+  const u32 t = s * g;
+  negate = ((t >> logn) & 1u) != 0;
+  return t & ((1u << logn) - 1u);
+}
+// one word of sigma_g on its way to the image: any word -> its canonical residue under the plan's policy, with the wrap's sign
+template <typename E, typename Pol> TN_HD E galois_scatter_word(E x, bool negate, const Arith<E>& ar) {
+  const E v = gadget_canon<E, Pol>(x, ar);
+  return negate ? galois_neg(v, ar.q) : v;
+}
+// the add-in at the store: (x + s) mod q for canonical x (an inverse transform's output) and canonical s (a word of sigma_g(a))
+template <typename E> TN_HD E galois_add_in(E x, E s, E q) { return csub((E)(x + s), q); }
 
 // Staging half, thread tid: `words` words of the tile's rows (in: the tile's first row) into the image, unit stride, GALOIS_UNROLL
 // loads requested before the first is used.  CANON: any word -> [0, q) with the canonical policy (gadget_decompose_kernel's).

@@ -175,7 +175,8 @@ inline hipError_t launch_persistent(const tn_plan* p, hipStream_t s, const void*
 }
 
 // kernels.hip (prepared operand: kernels_prepared.hip; transform domain: kernels_hat.hip; gadget: kernels_gadget.hip;
-// automorphisms: kernels_galois.hip; external product: kernels_extprod.hip; CMux rotation step: kernels_cmux.hip; blind rotation: kernels_blindrot.hip)
+// automorphisms: kernels_galois.hip; external product: kernels_extprod.hip; CMux rotation step: kernels_cmux.hip; blind rotation: kernels_blindrot.hip;
+// automorphism key switch: kernels_galoisks.hip)
 bool fused_supported(u32 logn, int elem_bytes);
 const char* fused_kernel_name(const tn_plan* p);
 const char* cg_kernel_name(const tn_plan* p, int group, int layout);
@@ -216,6 +217,10 @@ hipError_t launch_polydot_cmux(const tn_plan* p, const void* a, const uint32_t* 
 // c may be a itself
 hipError_t launch_polydot_blindrot(const tn_plan* p, const void* a, const uint32_t* exps, const void* bhat, void* c, size_t batch, size_t steps,
                                    size_t terms, tn::u32 base_log, bool balanced, hipStream_t s);
+// automorphism key switch (kernels_galoisks.hip; tn_poly_galois_keyswitch_prepared_dev, fused plans only): a, c [batch][2][n],
+// c[r][o] = [o == 0] sigma_g(a[r][0]) + sum_j digit_j(sigma_g(a[r][1])) * b[shared ? 0 : r][o][j], o < 2; galois odd, below 2n
+hipError_t launch_polydot_galoisks(const tn_plan* p, const void* a, uint32_t galois, const void* bhat, bool shared, void* c, size_t batch, size_t terms,
+                                   tn::u32 base_log, bool balanced, hipStream_t s);
 // ring automorphisms a(x) -> a(x^g) (kernels_galois.hip): count images of every row, out[r][m] = sigma_{galois[m]}(row r); on
 // coefficient rows (tn_automorphism_dev: every plan) and on prepared rows (tn_automorphism_prepared_dev: fused plans only)
 hipError_t launch_automorphism(const tn_plan* p, const void* a, void* out, size_t batch, const uint32_t* galois, size_t count, hipStream_t s);

@@ -45,7 +45,7 @@ EXPORTED_SYMBOLS = (
     "tn_gadget_decompose_dev", "tn_poly_gadget_dot_prepared_dev", "tn_poly_gadget_multidot_prepared_dev",
     "tn_poly_external_product_prepared_dev",
     "tn_monomial_mul_dev", "tn_poly_cmux_rotate_prepared_dev", "tn_poly_blind_rotate_prepared_dev",
-    "tn_automorphism_dev", "tn_automorphism_prepared_dev",
+    "tn_automorphism_dev", "tn_automorphism_prepared_dev", "tn_poly_galois_keyswitch_prepared_dev",
     "tn_plan_export_table", "tn_ntt_forward_dev", "tn_ntt_inverse_dev",
     "tn_ntt_forward_host", "tn_ntt_inverse_host", "tn_ntt_forward_trace_host", "tn_twisted_ntt_forward_dev",
     "tn_twisted_ntt_forward_host", "tn_schoolbook_host",
@@ -112,6 +112,7 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.tn_poly_blind_rotate_prepared_dev.argtypes = [vp, vp, vp, vp, vp, sz, sz, sz, sz, u32, u32, vp]
     lib.tn_automorphism_dev.argtypes = [vp, vp, vp, sz, ctypes.POINTER(u32), sz, vp]
     lib.tn_automorphism_prepared_dev.argtypes = [vp, vp, vp, sz, ctypes.POINTER(u32), sz, vp]
+    lib.tn_poly_galois_keyswitch_prepared_dev.argtypes = [vp, vp, u32, vp, sz, vp, sz, sz, u32, u32, vp]
     lib.tn_schoolbook_dev.argtypes = [vp, vp, vp, vp, sz, vp]
     lib.tn_plan_export_table.argtypes = [vp, ci, vp]
     for name in ("tn_ntt_forward_dev", "tn_ntt_inverse_dev", "tn_twisted_ntt_forward_dev"):
@@ -626,6 +627,43 @@ class Plan:
                                                                      c.data_ptr(), batch, comps, terms, int(base_log),
                                                                      GADGET_BALANCED if balanced else 0, self._stream_ptr(stream)))
         return self._result(c.reshape(batch, comps, self.n) if host else c, host, one, out)
+
+    def poly_galois_keyswitch_prepared(self, a, galois, prepared: PreparedOperand, terms, base_log, balanced=False, out=None, stream=None):
+        """The homomorphic automorphism of RLWE ciphertexts from ONE launch (tn_poly_galois_keyswitch_prepared_dev):
+        c[r][0] = sigma_g(a[r][0]) + sum_j digit_j(sigma_g(a[r][1])) * b[r][0][j], c[r][1] = sum_j digit_j(sigma_g(a[r][1])) * b[r][1][j].
+        a is (batch, 2, n), or (2, n) for one ciphertext, host values or a device tensor; galois is one odd integer below 2n; the
+        prepared operand has batch * 2 * terms rows ([batch][2][terms]), or 2 * terms rows that every row is multiplied by (the
+        layout of poly_gadget_multidot_prepared with outs = 2).  Returns (batch, 2, n) or (2, n), bit-identical to automorphism
+        on both components, poly_gadget_multidot_prepared on the rotated second one and the addition mod q.  out must not be a."""
+        import torch
+        self._own_prepared(prepared, "poly_galois_keyswitch_prepared", "key")
+        host = not _is_torch(a)
+        if host:
+            a = np.asarray(a)
+        if a.ndim not in (2, 3) or a.shape[-1] != self.n or a.shape[-2] != 2:
+            raise ValueError(f"Expected a of shape (batch, 2, {self.n}) or (2, {self.n})")
+        one = a.ndim == 2
+        batch = 1 if one else int(a.shape[0])
+        if host:
+            a = self.to_device(a.reshape(batch * 2, self.n))
+        else:
+            if not a.is_contiguous():
+                raise TinyNttError(TN_EINVAL, f"a: need a contiguous tensor of {self.elem_bytes}-byte integers")
+            self._dev_rows(a.reshape(batch * 2, self.n), "a")
+        terms, g = int(terms), int(galois)
+        if terms < 1:
+            raise ValueError(f"Expected terms >= 1, got {terms}")
+        if not 0 <= g < 2 ** 32:
+            raise ValueError(f"Expected a Galois element below 2n = {2 * self.n}, got {g}")
+        sets = self._sets(prepared, batch, 2 * terms, "key")
+        c = out if out is not None else torch.empty((batch, 2, self.n), dtype=self.torch_dtype, device=a.device)
+        if not _is_torch(c) or c.numel() != batch * 2 * self.n or not c.is_contiguous():
+            raise ValueError(f"Expected an output of {batch} x 2 rows of {self.n} coefficients")
+        self._dev_rows(c.reshape(batch * 2, self.n), "out")        # on the device, the plan's words: poly_gadget_dot_prepared's check
+        _check(self._lib, self._lib.tn_poly_galois_keyswitch_prepared_dev(self._h, a.data_ptr(), g, prepared.tensor.data_ptr(), sets, c.data_ptr(),
+                                                                          batch, terms, int(base_log), GADGET_BALANCED if balanced else 0,
+                                                                          self._stream_ptr(stream)))
+        return self._result(c.reshape(batch, 2, self.n) if host else c, host, one, out)
 
     def blind_rotate(self, acc, exps, prepared: PreparedOperand, terms, base_log, balanced=False, stream=None):
         """acc <- acc + RGSW_k [x] ((X^exps[k][r] - 1) * acc) for k = 0 .. steps - 1: poly_cmux_rotate_prepared step by step over two
