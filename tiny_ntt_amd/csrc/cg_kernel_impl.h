@@ -36,6 +36,20 @@ namespace tn {
 constexpr int CG_FLAG_RESTAGE = 0x100;   // or-ed into the kernel's mode: omega^(n/2) != -1 (any-psi plans): the inverse transform of a
                                          // product reads a re-staged inverse table instead of the forward one backwards
 
+// Every workgroup barrier of this kernel: s_waitcnt lgkmcnt(0) spelled out, then __syncthreads().  The release fence of
+// __syncthreads() asks for that wait (a wave's LDS writes have landed before it arrives) and the compiler normally emits it,
+// but not on every path: at GROUP 1 / 32-bit lanes the barrier at the head of the trip loop of the twisted forward transform
+// was reached over the loop's back-edge, straight from the column writes, with the only wait in front of the loop.  A wave
+// then passed the barrier with its writes in flight and another read the image before they landed: about 6 rows in 100,000
+// wrong at n = 1024 and n = 2048, one wave's column of one trip each (tests/test_gpu_cg_rows.py, F1024-twisted_ntt_forward-cg).
+// (gfx9 encoding: vmcnt 63, expcnt 7, lgkmcnt 0; where the compiler's own wait is there this one costs an issue slot.)
+__device__ __forceinline__ void cg_barrier() {
+#if defined(__HIP_DEVICE_COMPILE__)
+  __builtin_amdgcn_s_waitcnt(0xc07f);
+#endif
+  __syncthreads();
+}
+
 // Lane-steps one thread runs per trip.  Workgroups have n / (2 GROUP) threads up to 1024; beyond that a thread takes
 // several lane-steps (GROUP = 1: two at n = 4096).  BIG: the n = 8192 instantiations of GROUP 1 and 2 (twice the
 // lane-steps per thread; own kernels so that the n <= 4096 ones keep their register budget).
@@ -103,10 +117,10 @@ cg_kernel(const Arith<E> ar, u32 logn_rt, int mode_flags, const typename TwOf<E>
   unsigned long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, st_bar = 0, st_last = __builtin_amdgcn_s_memtime();
   const unsigned long long st_begin = st_last, st_rbegin = __builtin_amdgcn_s_memrealtime();
 #define TN_STAMP(k) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); st_acc[k] += t_ - st_last; st_last = t_; } while (0)
-#define TN_BARRIER() do { const unsigned long long t0_ = __builtin_amdgcn_s_memtime(); __syncthreads(); st_bar += __builtin_amdgcn_s_memtime() - t0_; } while (0)
+#define TN_BARRIER() do { const unsigned long long t0_ = __builtin_amdgcn_s_memtime(); cg_barrier(); st_bar += __builtin_amdgcn_s_memtime() - t0_; } while (0)
 #else
 #define TN_STAMP(k) do { } while (0)
-#define TN_BARRIER() __syncthreads()
+#define TN_BARRIER() cg_barrier()
 #endif
 
   // x: one lane-step's registers in bit-reversed order (x[brvL(e')] = element ls + e' TP of the input list, cg_ntt.py:39)
@@ -417,7 +431,7 @@ cg_kernel(const Arith<E> ar, u32 logn_rt, int mode_flags, const typename TwOf<E>
   };
   publish(0u, blockIdx.x * chunk);
   stage_table(mode == CG_NTT_INV ? om_inv : om_fwd);
-  __syncthreads();
+  cg_barrier();
 
   typedef std::integral_constant<bool, true> True;
   typedef std::integral_constant<bool, false> False;
@@ -524,7 +538,7 @@ cg_kernel(const Arith<E> ar, u32 logn_rt, int mode_flags, const typename TwOf<E>
       }
       load_row(xn, a, nrow, zero);
     }
-    if (restage) { __syncthreads(); stage_table(om_inv); }         // (the transform's first barrier orders the staging before its first read)
+    if (restage) { cg_barrier(); stage_table(om_inv); }         // (the transform's first barrier orders the staging before its first read)
     transform(xb, om_inv, !restage, nullptr);                      // :90 (:72-73)
     TN_STAMP(4);
     sched_fence();
@@ -537,7 +551,7 @@ cg_kernel(const Arith<E> ar, u32 logn_rt, int mode_flags, const typename TwOf<E>
       else store_row(xb, row, K1(), zero, tw_out);
     }
     TN_STAMP(5);
-    if (restage) { __syncthreads(); stage_table(om_fwd); }
+    if (restage) { cg_barrier(); stage_table(om_fwd); }
   };
   while (row < batch) {
     next = wave_uniform(lds_next[slot]);                           // published at least one workgroup barrier ago
@@ -569,7 +583,7 @@ cg_kernel(const Arith<E> ar, u32 logn_rt, int mode_flags, const typename TwOf<E>
         else { transform(xa, om_fwd, false, tr); store_row(xa, row, K0(), zero, tw_out); }
       }
     }
-    if (ntrips == 1) __syncthreads();                              // (a single trip has no barrier of its own between the slot's write and its read)
+    if (ntrips == 1) cg_barrier();                                 // (a single trip has no barrier of its own between the slot's write and its read)
     row = next; slot ^= 1u;
   }
   if constexpr (DEFER) { if (have_prev) emit_row(vprev, prev_row, 0u); }
