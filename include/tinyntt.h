@@ -595,6 +595,78 @@ tn_status tn_poly_galois_keyswitch_prepared_dev(tn_plan *plan, const void *a, ui
                                                 void *c, size_t batch, size_t terms, uint32_t base_log, uint32_t flags, void *stream);
 
 /*
+ * THE LWE ENDS OF A PROGRAMMABLE BOOTSTRAP: the modulus switch that turns an LWE ciphertext into the exponents of a blind
+ * rotation (tn_lwe_modswitch_dev), the sample extraction that takes an LWE ciphertext out of the rotated accumulator
+ * (tn_sample_extract_dev) and the LWE-to-LWE key switch back to the small key (tn_lwe_keyswitch_dev).  With tn_monomial_mul_dev
+ * and tn_poly_blind_rotate_prepared_dev (or a loop over tn_poly_cmux_rotate_prepared_dev) they make a TFHE-style bootstrap that
+ * never leaves the library: LWE ciphertexts in, LWE ciphertexts under the same key out.
+ *
+ * Conventions.
+ *   - An LWE ciphertext of dimension d is a row of d + 1 words of the plan's element type, a_0 .. a_{d-1}, b.  Rows are dense,
+ *     [batch][d + 1].  Its phase is b + sum_i a_i s_i mod q.
+ *   - An RLWE ciphertext is [2][n] with phase c0 + c1 s: the convention tn_poly_galois_keyswitch_prepared_dev implies.
+ *   - With these the three calls and the blind rotation compose without a negation.  A caller with the b - <a, s> convention
+ *     negates the key.
+ *   - Every input word is taken mod q (any word value is accepted); outputs are canonical residues in [0, q).
+ *   - All three calls work on EVERY plan (general and omega-only plans included): they need only n, q and the element width,
+ *     as tn_gadget_decompose_dev and tn_automorphism_dev do.  LWE dimensions are independent of n and at most TN_LWE_MAX_DIM.
+ *
+ * tn_lwe_modswitch_dev: lwe is [batch][dim + 1]; exps is a device uint32_t array [dim + 1][batch], TRANSPOSED on purpose: rows
+ * 0 .. dim - 1 are exactly the exps operand of tn_poly_blind_rotate_prepared_dev (steps = dim), row dim is the body's exponent,
+ * for tn_monomial_mul_dev.  exps[i][r] = floor((2n x + floor(q / 2)) / q) mod 2n with x = lwe[r][i] mod q and n the plan's,
+ * computed exactly (2n x does not fit a word: long division, one quotient bit per step).
+ *
+ * tn_sample_extract_dev: a is [batch][2][n], lwe is [batch][n + 1]; index is passed by value and must be below n.
+ *     lwe[r][i] = a[r][1][index - i] mod q                      for i <= index,
+ *     lwe[r][i] = (q - a[r][1][n + index - i] mod q) mod q      for index < i < n   (a zero stays 0),
+ *     lwe[r][n] = a[r][0][index] mod q.
+ * The phase of lwe[r] under the coefficients of s is coefficient `index` of a[r][0] + a[r][1] s.  The kernel's index into a row
+ * is masked besides: no value of index could cause an out-of-bounds access.
+ *
+ * tn_lwe_keyswitch_dev: lwe is [batch][n_in + 1]; ksk is [n_in][terms][n_out + 1] words of the plan's type, a plain array (any
+ * word values), not a prepared operand; out is [batch][n_out + 1]:
+ *     out[r][k] = ( [k == n_out] b_r + sum_{i < n_in} sum_{j < terms} d_j(a_r[i]) * ksk[i][j][k] ) mod q,
+ * a_r[i] = lwe[r][i] mod q, b_r = lwe[r][n_in] mod q.  d_j is the library's own digit (GADGET decomposition above: base 2^base_log,
+ * unsigned or TN_GADGET_BALANCED with the carry running up the digits and the last carry dropped), used as a signed integer,
+ * which equals its canonical residue mod q.  ksk[i][j] is an LWE encryption of s_i 2^(j base_log) under the output key.  n_in and
+ * n_out are independent of the plan's n.  base_log above 32 is TN_EUNSUPPORTED (the kernel keeps digits as 32-bit words; LWE key
+ * switches use bases of 2^2 to 2^8), and so is n_in * terms above 2^22 (the kernel's 128-bit sums are not reduced on the way).
+ *
+ * Status, in this order.  All three: TN_EINVAL a NULL plan.
+ *   tn_lwe_modswitch_dev: TN_EINVAL dim outside [1, TN_LWE_MAX_DIM]; batch * (dim + 1) > 2^31 - 1; batch == 0 succeeds and
+ *     launches nothing; TN_EINVAL a NULL buffer; exps overlapping lwe (byte ranges).
+ *   tn_sample_extract_dev: TN_EINVAL index >= n; batch * (n + 1) > 2^31 - 1; batch == 0 succeeds; TN_EINVAL a NULL buffer; lwe
+ *     overlapping a.
+ *   tn_lwe_keyswitch_dev: TN_EINVAL n_in, then n_out, outside [1, TN_LWE_MAX_DIM]; everything the gadget calls refuse, in their
+ *     order (terms == 0, a flag bit other than TN_GADGET_BALANCED, base_log == 0 or 2^base_log >= q, (terms - 1) * base_log >= 64,
+ *     n_in * terms > 2^31 - 1); TN_EUNSUPPORTED base_log > 32; TN_EUNSUPPORTED n_in * terms > 2^22 (unreachable with today's
+ *     limits, 2^16 and 64 terms: the bound stands for the day one of them grows); TN_EINVAL
+ *     batch * (n_in + 1) or batch * (n_out + 1) > 2^31 - 1; batch == 0 succeeds; TN_EINVAL a NULL buffer; out overlapping lwe or ksk.
+ * The calls enqueue on the stream and return; none allocates, copies or synchronises, and all may be stream-captured.
+ *
+ * When to use which (MI355X, profiles/lwe_ab.txt, tools/gpu_lwe.py; one process per point, 9 interleaved repeats, outputs compared
+ * first; n = 1024 / 24-bit with n_out = 512 and n = 2048 / 60-bit with n_out = 768, batch 256 and 4,096; all by disjoint ranges):
+ *   - the key switch at 60-bit: tn_lwe_keyswitch_dev is the only route (torch has no 128-bit sum): 2,157 us at batch 256 and 9,855 us
+ *     at batch 4,096 for terms 4, w 15 (0.75 and 2.6 T multiply-adds / s), 4 - 8 % of the whole Plan.bootstrap on the same rows.
+ *   - the key switch at 24-bit: a float64 torch.matmul on digits cut in torch (exact while the sums stay below 2^53) is FASTER at
+ *     all four points, x 3.6 - 6.4 (98 against 633 us at batch 256, terms 3, w 8; 771 against 2,980 us at batch 4,096, terms 6, w 4):
+ *     use it there.  It is also the figure a matrix-core formulation of this call starts from.
+ *   - batch 256 runs at a seventh to a third of batch 4,096's multiply-add rate: 96 - 128 workgroups on 256 CUs; no split over i exists.
+ *   - the two element-wise calls take 9 - 28 us per call, the enqueue through Python included, x 1.7 - 6.8 of a device-to-device copy
+ *     of the same bytes (3 - 17 us).  The modulus switch takes the same 15 us at batch 256 and 4,096: most of that is not the kernel;
+ *     the cause was not isolated.
+ *   - not measured: n = 256, n = 8192, the canonical policy, other n_out, balanced key-switch digits.
+ *
+ * No *_host form, no tn_multi_* form, no key-switch key per row, no modulus switch to anything but the plan's 2n, no RLWE-to-LWE
+ * packing.  The reference has no counterpart.
+ */
+#define TN_LWE_MAX_DIM 65536
+tn_status tn_lwe_modswitch_dev(tn_plan *plan, const void *lwe, uint32_t *exps, size_t batch, size_t dim, void *stream);
+tn_status tn_sample_extract_dev(tn_plan *plan, const void *a, void *lwe, size_t batch, uint32_t index, void *stream);
+tn_status tn_lwe_keyswitch_dev(tn_plan *plan, const void *lwe, const void *ksk, void *out, size_t batch, size_t n_in, size_t n_out,
+                               size_t terms, uint32_t base_log, uint32_t flags, void *stream);
+
+/*
  * The *_host entry points cut the batch into chunks that flow H2D -> kernel -> D2H on three
  * streams through a fixed set of device staging slots (copies overlap the kernels when the host
  * buffers are pinned; device staging stays bounded whatever the batch).  rows = rows per chunk,

@@ -14,6 +14,10 @@ namespace tn {
 // (lazy: the plan's policy, which names its fused shape together with n and elem_bytes; only check_blind_rotate asks)
 struct ApiPlan { uint32_t n; int elem_bytes; bool has_fused, omega_only; uint64_t q; bool lazy = false; };     // a NULL plan: n == 0
 
+// what the LWE key switch's kernel holds (lwe_core.h): digits as 32-bit words; 128-bit sums of n_in * terms terms below 2^32 2^64
+constexpr size_t LWE_KS_MAX_SLOTS = (size_t)1 << 22;
+constexpr uint32_t LWE_KS_MAX_BASE_LOG = 32;
+
 struct KernelPick { bool known, fused; int group, layout; };     // layout: CgLayout, cg_core.h (0 linear, 1 padded, 2 swizzled)
 // The kernel a variant names; TN_VARIANT_AUTO is the fused kernel where the plan has it (and no trace is wanted), else CG.
 static inline KernelPick pick_kernel(const ApiPlan& v, tn_variant variant, bool trace = false) {
@@ -107,6 +111,27 @@ struct __attribute__((visibility("hidden"))) ApiCheck {          // (hidden, sta
   bool apart(const void* out, size_t out_rows, const void* in, size_t in_rows, const char* noun) {
     const uintptr_t o = (uintptr_t)out, i = (uintptr_t)in, row = (uintptr_t)v.n * (uintptr_t)v.elem_bytes;
     return !(o < i + in_rows * row && i < o + out_rows * row) || fail(TN_EINVAL, (std::string("output must not alias or overlap ") + noun).c_str());
+  }
+  // The LWE calls (tn_lwe_modswitch_dev, tn_sample_extract_dev, tn_lwe_keyswitch_dev): a dimension is 1 .. TN_LWE_MAX_DIM; the
+  // extracted coefficient lies in the row; the key switch keeps digits as 32-bit words and sums of n_in * terms terms, each
+  // below 2^32 2^64, in 128 bits: 2^22 of them stay below 2^118 (LWE_KS_MAX_SLOTS, LWE_KS_MAX_BASE_LOG above).  With
+  // TN_LWE_MAX_DIM = 2^16 and the gadget rule's terms <= 64 no call reaches lwe_sum's bound today: it stands for the day either grows.
+  bool lwe_dim(size_t d, const char* name) {
+    return (d >= 1 && d <= TN_LWE_MAX_DIM) || fail(TN_EINVAL, (std::string(name) + " must be between 1 and TN_LWE_MAX_DIM (65536)").c_str());
+  }
+  bool lwe_index(uint32_t index) { return index < v.n || fail(TN_EINVAL, "index must be below n"); }
+  bool lwe_digits(uint32_t base_log) {
+    return base_log <= LWE_KS_MAX_BASE_LOG ||
+           fail(TN_EUNSUPPORTED, "base_log above 32 is not supported: the kernel keeps digits as 32-bit words (LWE key switches use bases of 2^2 to 2^8)");
+  }
+  bool lwe_sum(size_t n_in, size_t terms_) {
+    return n_in * terms_ <= LWE_KS_MAX_SLOTS ||
+           fail(TN_EUNSUPPORTED, "n_in * terms above 2^22 is not supported: a 128-bit sum holds 2^22 terms below 2^32 * 2^64");
+  }
+  // byte ranges of buffers that are not rows of n words
+  bool apart_bytes(const void* out, size_t out_bytes, const void* in, size_t in_bytes, const char* noun) {
+    const uintptr_t o = (uintptr_t)out, i = (uintptr_t)in;
+    return !(o < i + in_bytes && i < o + out_bytes) || fail(TN_EINVAL, (std::string("output must not alias or overlap ") + noun).c_str());
   }
   // tn_poly_mult_dev words these two without its name (named = false)
   bool kernel(const KernelPick& k, bool trace, bool named = true) {
@@ -219,6 +244,28 @@ static inline bool check_galois_keyswitch(ApiCheck& k, const void* a, uint32_t g
   return k.plan() && k.fused() && k.galois(&galois, 1) && k.gadget(rows_times(batch, 2), terms, base_log, flags, "batch * 2 * terms") &&
          k.work(batch) && k.buffers(a && bhat && c) && k.sets(sets, batch, "bhat_sets", "one set of operands for every row") &&
          k.apart(c, batch * 2, a, batch * 2, "an input") && k.apart(c, batch * 2, bhat, sets * 2 * terms, "an input");
+}
+// tn_lwe_modswitch_dev: lwe has batch * (dim + 1) words of the plan's type, exps as many 32-bit words.  Every plan.
+static inline bool check_lwe_modswitch(ApiCheck& k, const void* lwe, const void* exps, size_t batch, size_t dim) {
+  return k.plan() && k.lwe_dim(dim, "dim") && k.rows(batch, dim + 1, "batch * (dim + 1)", "words") && k.work(batch) && k.buffers(lwe && exps) &&
+         k.apart_bytes(exps, batch * (dim + 1) * 4, lwe, batch * (dim + 1) * (size_t)k.v.elem_bytes, "the input");
+}
+// tn_sample_extract_dev: a has batch * 2 rows, lwe batch * (n + 1) words; index by value, below n.  Every plan.
+static inline bool check_sample_extract(ApiCheck& k, const void* a, const void* lwe, size_t batch, uint32_t index) {
+  const size_t word = (size_t)k.v.elem_bytes;
+  return k.plan() && k.lwe_index(index) && k.rows(batch, (size_t)k.v.n + 1, "batch * (n + 1)", "words") && k.work(batch) && k.buffers(a && lwe) &&
+         k.apart_bytes(lwe, batch * ((size_t)k.v.n + 1) * word, a, batch * 2 * (size_t)k.v.n * word, "the input");
+}
+// tn_lwe_keyswitch_dev: the two dimensions, then what the gadget calls ask with n_in * terms key rows for the row limit, then
+// what the kernel's digits and sums hold, then the word counts of lwe and out; ksk has n_in * terms * (n_out + 1) words.  Every plan.
+static inline bool check_lwe_keyswitch(ApiCheck& k, const void* lwe, const void* ksk, const void* out, size_t batch, size_t n_in, size_t n_out,
+                                       size_t terms, uint32_t base_log, uint32_t flags) {
+  const size_t word = (size_t)k.v.elem_bytes;
+  return k.plan() && k.lwe_dim(n_in, "n_in") && k.lwe_dim(n_out, "n_out") && k.gadget(n_in, terms, base_log, flags, "n_in * terms", "key rows") &&
+         k.lwe_digits(base_log) && k.lwe_sum(n_in, terms) && k.rows(batch, n_in + 1, "batch * (n_in + 1)", "words") &&
+         k.rows(batch, n_out + 1, "batch * (n_out + 1)", "words") && k.work(batch) && k.buffers(lwe && ksk && out) &&
+         k.apart_bytes(out, batch * (n_out + 1) * word, lwe, batch * (n_in + 1) * word, "an input") &&
+         k.apart_bytes(out, batch * (n_out + 1) * word, ksk, n_in * terms * (n_out + 1) * word, "an input");
 }
 static inline bool check_pointwise(ApiCheck& k, const void* a, const void* b, const void* c, size_t batch) {      // in place is allowed
   return k.plan() && k.rows_wide(batch) && k.buffers(!batch || (a && b && c));

@@ -343,6 +343,29 @@ extern "C" tn_status tn_automorphism_prepared_dev(tn_plan* p, const void* xhat, 
   return TN_OK;
 }
 
+// ---- the LWE ends of a bootstrap: modulus switch to 2n, sample extraction, LWE-to-LWE key switch (every plan) ----------------
+extern "C" tn_status tn_lwe_modswitch_dev(tn_plan* p, const void* lwe, uint32_t* exps, size_t batch, size_t dim, void* stream) {
+  TN_CHECK("tn_lwe_modswitch_dev", check_lwe_modswitch(k, lwe, exps, batch, dim));
+  TN_ON_DEVICE(p);
+  TN_HIP(launch_lwe_modswitch(p, lwe, exps, batch, dim, pick_stream(p, stream)));
+  return TN_OK;
+}
+
+extern "C" tn_status tn_sample_extract_dev(tn_plan* p, const void* a, void* lwe, size_t batch, uint32_t index, void* stream) {
+  TN_CHECK("tn_sample_extract_dev", check_sample_extract(k, a, lwe, batch, index));
+  TN_ON_DEVICE(p);
+  TN_HIP(launch_lwe_sample_extract(p, a, lwe, batch, index, pick_stream(p, stream)));
+  return TN_OK;
+}
+
+extern "C" tn_status tn_lwe_keyswitch_dev(tn_plan* p, const void* lwe, const void* ksk, void* out, size_t batch, size_t n_in, size_t n_out,
+                                          size_t terms, uint32_t base_log, uint32_t flags, void* stream) {
+  TN_CHECK("tn_lwe_keyswitch_dev", check_lwe_keyswitch(k, lwe, ksk, out, batch, n_in, n_out, terms, base_log, flags));
+  TN_ON_DEVICE(p);
+  TN_HIP(launch_lwe_keyswitch(p, lwe, ksk, out, batch, n_in, n_out, terms, base_log, (flags & TN_GADGET_BALANCED) != 0, pick_stream(p, stream)));
+  return TN_OK;
+}
+
 extern "C" tn_status tn_pointwise_mul_dev(tn_plan* p, const void* a, const void* b, void* c, size_t batch, void* stream) {
   TN_CHECK("tn_pointwise_mul_dev", check_pointwise(k, a, b, c, batch));
   TN_ON_DEVICE(p);

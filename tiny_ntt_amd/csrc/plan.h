@@ -176,7 +176,7 @@ inline hipError_t launch_persistent(const tn_plan* p, hipStream_t s, const void*
 
 // kernels.hip (prepared operand: kernels_prepared.hip; transform domain: kernels_hat.hip; gadget: kernels_gadget.hip;
 // automorphisms: kernels_galois.hip; external product: kernels_extprod.hip; CMux rotation step: kernels_cmux.hip; blind rotation: kernels_blindrot.hip;
-// automorphism key switch: kernels_galoisks.hip)
+// automorphism key switch: kernels_galoisks.hip; LWE modulus switch, sample extraction and key switch: kernels_lwe.hip)
 bool fused_supported(u32 logn, int elem_bytes);
 const char* fused_kernel_name(const tn_plan* p);
 const char* cg_kernel_name(const tn_plan* p, int group, int layout);
@@ -226,6 +226,13 @@ hipError_t launch_polydot_galoisks(const tn_plan* p, const void* a, uint32_t gal
 hipError_t launch_automorphism(const tn_plan* p, const void* a, void* out, size_t batch, const uint32_t* galois, size_t count, hipStream_t s);
 hipError_t launch_automorphism_prepared(const tn_plan* p, const void* xhat, void* out, size_t rows, const uint32_t* galois, size_t count,
                                         hipStream_t s);
+// the LWE ends of a bootstrap (kernels_lwe.hip; every plan).  tn_lwe_modswitch_dev: lwe [batch][dim + 1] -> exps [dim + 1][batch],
+// round(2n x / q) mod 2n.  tn_sample_extract_dev: a [batch][2][n] -> lwe [batch][n + 1], coefficient `index` (below n) of the
+// phase.  tn_lwe_keyswitch_dev: out[r][k] = [k == n_out] b_r + sum_i sum_j digit_j(a_r[i]) * ksk[i][j][k], ksk [n_in][terms][n_out + 1]
+hipError_t launch_lwe_modswitch(const tn_plan* p, const void* lwe, uint32_t* exps, size_t batch, size_t dim, hipStream_t s);
+hipError_t launch_lwe_sample_extract(const tn_plan* p, const void* a, void* lwe, size_t batch, tn::u32 index, hipStream_t s);
+hipError_t launch_lwe_keyswitch(const tn_plan* p, const void* lwe, const void* ksk, void* out, size_t batch, size_t n_in, size_t n_out, size_t terms,
+                                tn::u32 base_log, bool balanced, hipStream_t s);
 hipError_t launch_cg(const tn_plan* p, int mode, int group, int layout, const void* a, const void* b, void* out,
                      void* trace, size_t batch, hipStream_t s);
 hipError_t launch_pointwise(const tn_plan* p, const void* a, const void* b, void* c, size_t batch, hipStream_t s);

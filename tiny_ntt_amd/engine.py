@@ -46,6 +46,7 @@ EXPORTED_SYMBOLS = (
     "tn_poly_external_product_prepared_dev",
     "tn_monomial_mul_dev", "tn_poly_cmux_rotate_prepared_dev", "tn_poly_blind_rotate_prepared_dev",
     "tn_automorphism_dev", "tn_automorphism_prepared_dev", "tn_poly_galois_keyswitch_prepared_dev",
+    "tn_lwe_modswitch_dev", "tn_sample_extract_dev", "tn_lwe_keyswitch_dev",
     "tn_plan_export_table", "tn_ntt_forward_dev", "tn_ntt_inverse_dev",
     "tn_ntt_forward_host", "tn_ntt_inverse_host", "tn_ntt_forward_trace_host", "tn_twisted_ntt_forward_dev",
     "tn_twisted_ntt_forward_host", "tn_schoolbook_host",
@@ -113,6 +114,9 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.tn_automorphism_dev.argtypes = [vp, vp, vp, sz, ctypes.POINTER(u32), sz, vp]
     lib.tn_automorphism_prepared_dev.argtypes = [vp, vp, vp, sz, ctypes.POINTER(u32), sz, vp]
     lib.tn_poly_galois_keyswitch_prepared_dev.argtypes = [vp, vp, u32, vp, sz, vp, sz, sz, u32, u32, vp]
+    lib.tn_lwe_modswitch_dev.argtypes = [vp, vp, vp, sz, sz, vp]
+    lib.tn_sample_extract_dev.argtypes = [vp, vp, vp, sz, u32, vp]
+    lib.tn_lwe_keyswitch_dev.argtypes = [vp, vp, vp, vp, sz, sz, sz, sz, u32, u32, vp]
     lib.tn_schoolbook_dev.argtypes = [vp, vp, vp, vp, sz, vp]
     lib.tn_plan_export_table.argtypes = [vp, ci, vp]
     for name in ("tn_ntt_forward_dev", "tn_ntt_inverse_dev", "tn_twisted_ntt_forward_dev"):
@@ -724,6 +728,144 @@ class Plan:
                                                                       batch, comps, steps, terms, int(base_log),
                                                                       GADGET_BALANCED if balanced else 0, self._stream_ptr(stream)))
         return c
+
+    # ---- the LWE ends of a bootstrap ------------------------------------------------
+    def _lwe_in(self, x, name, cols=None):
+        """LWE rows (batch, d + 1), or (d + 1,) for one ciphertext, host values (taken mod q) or a device tensor of any words ->
+        (contiguous device tensor (batch, d + 1), came from the host, one ciphertext).  cols: the row length expected."""
+        import torch
+        host = not _is_torch(x)
+        if host:
+            h = np.asarray(x)
+            if h.dtype == object or h.dtype.kind == "i":
+                h = np.array([int(v) % self.q for v in h.ravel()], dtype=self.dtype).reshape(h.shape)
+            elif h.dtype.kind != "u":
+                raise TypeError(f"{name}: words must be integers, got dtype {h.dtype}")
+            elif h.dtype.itemsize > self.elem_bytes:
+                h = np.mod(h, self.q)
+            h = np.ascontiguousarray(h, dtype=self.dtype)
+            x = torch.from_numpy(h.view(np.int32 if self.elem_bytes == 4 else np.int64)).to(f"cuda:{self.device}")
+        elif not x.is_cuda or x.element_size() != self.elem_bytes or not x.is_contiguous():
+            raise TinyNttError(TN_EINVAL, f"{name}: need a contiguous device tensor of {self.elem_bytes}-byte integers")
+        one = x.dim() == 1
+        if one:
+            x = x[None, :]
+        if x.dim() != 2 or x.shape[1] < 2 or (cols is not None and x.shape[1] != cols):
+            raise ValueError(f"Expected {name} of shape (batch, {cols if cols is not None else 'dim + 1'})")
+        return x, host, one
+
+    def _lwe_out(self, out, shape, device, dtype=None):
+        import torch
+        dtype = dtype or self.torch_dtype
+        c = out if out is not None else torch.empty(shape, dtype=dtype, device=device)
+        if not _is_torch(c) or not c.is_cuda or c.numel() != int(np.prod(shape)) or not c.is_contiguous() or c.dtype != dtype:
+            raise ValueError(f"Expected a contiguous device output of shape {tuple(shape)}")
+        return c
+
+    def lwe_modswitch(self, lwe, out=None, stream=None):
+        """The modulus switch of LWE ciphertexts to 2n (tn_lwe_modswitch_dev): lwe is (batch, dim + 1) rows a_0 .. a_{dim-1}, b,
+        host values or a device tensor of any words.  Returns the exponents TRANSPOSED, a 32-bit tensor (dim + 1, batch) with
+        exps[i][r] = floor((2n x + floor(q / 2)) / q) mod 2n, x = lwe[r][i] mod q: exps[:dim] is the exps operand of
+        poly_blind_rotate_prepared / blind_rotate, exps[dim] the body's exponent for monomial_mul.  Host rows in give a host
+        array out.  Works on every plan."""
+        import torch
+        x, host, _ = self._lwe_in(lwe, "lwe")
+        batch, dim = int(x.shape[0]), int(x.shape[1]) - 1
+        e = self._lwe_out(out, (dim + 1, batch), x.device, torch.int32)
+        _check(self._lib, self._lib.tn_lwe_modswitch_dev(self._h, x.data_ptr(), e.data_ptr(), batch, dim, self._stream_ptr(stream)))
+        return e.cpu().numpy().view(np.uint32) if host else e
+
+    def sample_extract(self, a, index=0, out=None, stream=None):
+        """The LWE ciphertext of coefficient `index` of the phase of RLWE ciphertexts (tn_sample_extract_dev): a is (batch, 2, n),
+        or (2, n) for one, phase c0 + c1 s; returns (batch, n + 1) rows (c1[index], c1[index - 1], .., c1[0], -c1[n - 1], ..,
+        -c1[index + 1], c0[index]) mod q, whose phase b + <a, s> under the coefficients of s is that coefficient.  Host values or
+        a device tensor in, the same kind out.  Works on every plan."""
+        host = not _is_torch(a)
+        if host:
+            a = np.asarray(a)
+        if a.ndim not in (2, 3) or a.shape[-1] != self.n or a.shape[-2] != 2:
+            raise ValueError(f"Expected a of shape (batch, 2, {self.n}) or (2, {self.n})")
+        one = a.ndim == 2
+        batch = 1 if one else int(a.shape[0])
+        if host:
+            a = self.to_device(a.reshape(batch * 2, self.n))
+        else:
+            if not a.is_contiguous():
+                raise TinyNttError(TN_EINVAL, f"a: need a contiguous tensor of {self.elem_bytes}-byte integers")
+            self._dev_rows(a.reshape(batch * 2, self.n), "a")
+        if not 0 <= int(index) < 2 ** 32:
+            raise ValueError(f"Expected an index below n = {self.n}, got {index}")
+        c = self._lwe_out(out, (batch, self.n + 1), a.device)
+        _check(self._lib, self._lib.tn_sample_extract_dev(self._h, a.data_ptr(), c.data_ptr(), batch, int(index), self._stream_ptr(stream)))
+        return self._result(c, host, one, out)
+
+    def lwe_keyswitch(self, lwe, ksk, n_out, terms, base_log, balanced=False, out=None, stream=None):
+        """The LWE-to-LWE key switch (tn_lwe_keyswitch_dev): lwe is (batch, n_in + 1), ksk is (n_in, terms, n_out + 1) words of the
+        plan's type, ksk[i][j] an LWE encryption of s_i 2^(j base_log) under the output key (a plain array, host values or a device
+        tensor); returns (batch, n_out + 1) with out[r][k] = [k == n_out] b_r + sum_i sum_j digit_j(a_r[i]) ksk[i][j][k] mod q, the
+        digits the gadget calls' (unsigned, or balanced).  n_in and n_out are independent of the plan's n.  Works on every plan."""
+        x, host, one = self._lwe_in(lwe, "lwe")
+        batch, n_in, n_out, terms = int(x.shape[0]), int(x.shape[1]) - 1, int(n_out), int(terms)
+        if terms < 1 or n_out < 1:
+            raise ValueError(f"Expected terms >= 1 and n_out >= 1, got {terms} and {n_out}")
+        if _is_torch(ksk):
+            k = ksk
+            if not k.is_cuda or k.element_size() != self.elem_bytes or not k.is_contiguous():
+                raise TinyNttError(TN_EINVAL, f"ksk: need a contiguous device tensor of {self.elem_bytes}-byte integers")
+        else:
+            k, _, _ = self._lwe_in(np.asarray(ksk).reshape(-1, n_out + 1), "ksk", n_out + 1)
+        if k.numel() != n_in * terms * (n_out + 1):
+            raise ValueError(f"Expected a key of shape ({n_in}, {terms}, {n_out + 1}), got {k.numel()} words")
+        c = self._lwe_out(out, (batch, n_out + 1), x.device)
+        _check(self._lib, self._lib.tn_lwe_keyswitch_dev(self._h, x.data_ptr(), k.data_ptr(), c.data_ptr(), batch, n_in, n_out, terms, int(base_log),
+                                                         GADGET_BALANCED if balanced else 0, self._stream_ptr(stream)))
+        return self._result(c, host, one, out)
+
+    def bootstrap(self, lwe, bsk: PreparedOperand, test_vector, ksk, *, terms, base_log, ks_terms, ks_base_log, balanced=False, ks_balanced=False,
+                  one_launch=False, stream=None):
+        """A programmable bootstrap of LWE ciphertexts, LWE in and LWE under the same key out, from the library's calls alone:
+          1. lwe_modswitch: exps (dim + 1, batch);
+          2. the accumulator (X^exps[dim] * test_vector, 0) from monomial_mul;
+          3. poly_blind_rotate_prepared when one_launch is set, else blind_rotate, over exps[:dim] with the bootstrap key bsk
+             (dim * 4 * terms prepared rows: RGSW encryptions of the key bits, one per step);
+          4. sample_extract at index 0: LWE of dimension n under the coefficients of the ring key;
+          5. lwe_keyswitch with ksk (n, ks_terms, dim + 1) back to dimension dim.
+        lwe is (batch, dim + 1), host values or a device tensor; test_vector one polynomial of n words, host or device; ksk host
+        or device words.  The two blind-rotation routes are bit-identical.  Which suits which batch (README, "Blind rotation"): one
+        launch keeps the accumulator on chip and wins where the batch leaves workgroups to spare; the step-by-step loop reads
+        each step's key once for the whole batch and is the route for large batches, and the only one where the accumulator does
+        not fit a workgroup's LDS (n = 8192 with 64-bit words).  Nothing synchronises between the steps.  stream: None (torch's
+        current stream), a torch.cuda.Stream or a raw HIP stream handle; the library's calls are enqueued on it and the method's
+        own torch work (the intermediates' allocations, the zero fill of the accumulator, the copy of the test vector) runs under
+        the same stream, so everything is ordered on it.  The plan's own stream ("plan") is refused: torch cannot run on it.
+        Returns (batch, dim + 1), a host array where lwe came from the host."""
+        import torch
+        if isinstance(stream, str):
+            raise ValueError("bootstrap: stream must be None, a torch.cuda.Stream or a raw stream handle (torch cannot run on the plan's own stream)")
+        if stream is not None:
+            ts = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(int(stream), device=self.device)
+            with torch.cuda.stream(ts):
+                return self.bootstrap(lwe, bsk, test_vector, ksk, terms=terms, base_log=base_log, ks_terms=ks_terms, ks_base_log=ks_base_log,
+                                      balanced=balanced, ks_balanced=ks_balanced, one_launch=one_launch, stream=None)
+        self._own_prepared(bsk, "bootstrap", "bootstrap key")
+        x, host, one = self._lwe_in(lwe, "lwe")
+        batch, dim = int(x.shape[0]), int(x.shape[1]) - 1
+        if bsk.rows != dim * 4 * int(terms):
+            raise ValueError(f"Expected a bootstrap key of {dim} x {4 * int(terms)} rows, got {bsk.rows}")
+        tv = test_vector if _is_torch(test_vector) else self.to_device(np.asarray(test_vector).reshape(1, self.n))
+        if self._dev_rows(tv.reshape(1, self.n) if tv.numel() == self.n else tv, "test_vector") != 1:
+            raise ValueError(f"Expected a test vector of {self.n} coefficients")
+        exps = self.lwe_modswitch(x, stream=stream)
+        tvs = torch.zeros((batch, 2, self.n), dtype=self.torch_dtype, device=x.device)
+        tvs[:, 0] = tv.reshape(self.n)
+        acc = self.monomial_mul(tvs, exps[dim], stream=stream)
+        if one_launch:
+            acc = self.poly_blind_rotate_prepared(acc, exps[:dim], bsk, terms, base_log, balanced, out=acc, stream=stream)
+        else:
+            acc = self.blind_rotate(acc, exps[:dim], bsk, terms, base_log, balanced, stream=stream)
+        big = self.sample_extract(acc, 0, stream=stream)
+        c = self.lwe_keyswitch(big, ksk, dim, ks_terms, ks_base_log, ks_balanced, stream=stream)
+        return self._result(c, host, one)
 
     # ---- ring automorphisms a(x) -> a(x^g) ----------------------------------------
     @staticmethod
