@@ -667,6 +667,42 @@ tn_status tn_lwe_keyswitch_dev(tn_plan *plan, const void *lwe, const void *ksk, 
                                size_t terms, uint32_t base_log, uint32_t flags, void *stream);
 
 /*
+ * THE LWE KEY SWITCH ON THE MATRIX CORES: the key prepared once as signed bytes (tn_lwe_ksk_prepare_dev), then any number of key
+ * switches with it (tn_lwe_keyswitch_prepared_dev) on the gfx950 int8 matrix instruction (v_mfma_i32_16x16x64_i8) with exact sums.
+ *
+ * Contract: out of tn_lwe_keyswitch_prepared_dev is word for word what tn_lwe_keyswitch_dev writes for the same lwe, the plain
+ * ksk that kprep was prepared from and the same terms, base_log and flags, on every plan and for any input words.  Both compute
+ * the same integer sum mod q; nothing is approximate.
+ *
+ * The prepared key is opaque and belongs to the plan (its q) and the build, as prepared operands do.  It is a pure function of
+ * (q, ksk mod q, n_in, n_out, terms): every key word is made canonical, replaced by its centred residue in (-q/2, q/2] and cut,
+ * from the low end, into L(q) balanced base-256 limbs in [-128, 128).  L limbs hold -128 (256^L - 1) / 255 .. 127 (256^L - 1) / 255,
+ * so L(q) is the smallest L with floor(q / 2) <= 127 (256^L - 1) / 255: 3 for q = 8380417 (the canonical residue would not fit:
+ * 127 (2^24 - 1) / 255 = 8355711 < q - 1), 8 for q = 2^60 - 2^14 + 1.  The limb planes lie in the matrix instruction's operand
+ * order, [ceil((n_out + 1) / 16)][ceil(n_in * terms / 64)][L][64 lanes][16 bytes], the padding filled with zero limbs:
+ * tn_lwe_ksk_prepared_bytes gives the size, padding included (host only; nothing is launched).  kprep must be aligned to 16 bytes.
+ *
+ * Digits are the library's own, as signed bytes: unsigned digits need base_log <= 7, TN_GADGET_BALANCED needs base_log <= 8;
+ * wider digits are TN_EUNSUPPORTED (tn_lwe_keyswitch_dev is the route).  n_in, n_out, terms and n_in * terms keep the limits of
+ * tn_lwe_keyswitch_dev (terms <= 64 for the two calls without a base_log).
+ *
+ * Status, in this order.  All three: TN_EINVAL a NULL plan; n_in, then n_out, outside [1, TN_LWE_MAX_DIM].
+ *   tn_lwe_ksk_prepared_bytes, tn_lwe_ksk_prepare_dev: TN_EINVAL terms == 0, terms > 64, n_in * terms > 2^31 - 1; TN_EUNSUPPORTED
+ *     n_in * terms > 2^22; then TN_EINVAL a NULL bytes, or a NULL buffer, kprep not aligned to 16 bytes, kprep (its
+ *     tn_lwe_ksk_prepared_bytes) overlapping ksk.
+ *   tn_lwe_keyswitch_prepared_dev: everything the gadget calls refuse, in their order, as tn_lwe_keyswitch_dev; TN_EUNSUPPORTED
+ *     digits wider than a signed byte; TN_EUNSUPPORTED n_in * terms > 2^22; TN_EINVAL batch * (n_in + 1) or batch * (n_out + 1)
+ *     > 2^31 - 1; batch == 0 succeeds and launches nothing; TN_EINVAL a NULL buffer; kprep not aligned to 16 bytes; out overlapping
+ *     lwe or kprep.  The call cannot see how many bytes lie behind kprep: the caller vouches for tn_lwe_ksk_prepared_bytes of them.
+ * The two device calls enqueue on the stream and return; neither allocates, copies or synchronises, and both may be stream-captured.
+ * When to use which: README, "LWE ends of the bootstrap" (profiles/lwe_mfma_ab.txt, tools/gpu_lwe_mfma.py).
+ */
+tn_status tn_lwe_ksk_prepared_bytes(tn_plan *plan, size_t n_in, size_t n_out, size_t terms, size_t *bytes);
+tn_status tn_lwe_ksk_prepare_dev(tn_plan *plan, const void *ksk, void *kprep, size_t n_in, size_t n_out, size_t terms, void *stream);
+tn_status tn_lwe_keyswitch_prepared_dev(tn_plan *plan, const void *lwe, const void *kprep, void *out, size_t batch, size_t n_in, size_t n_out,
+                                        size_t terms, uint32_t base_log, uint32_t flags, void *stream);
+
+/*
  * The *_host entry points cut the batch into chunks that flow H2D -> kernel -> D2H on three
  * streams through a fixed set of device staging slots (copies overlap the kernels when the host
  * buffers are pinned; device staging stays bounded whatever the batch).  rows = rows per chunk,

@@ -18,6 +18,32 @@ struct ApiPlan { uint32_t n; int elem_bytes; bool has_fused, omega_only; uint64_
 constexpr size_t LWE_KS_MAX_SLOTS = (size_t)1 << 22;
 constexpr uint32_t LWE_KS_MAX_BASE_LOG = 32;
 
+// What the prepared key switch holds (lwe_mfma_core.h: signed bytes into the int8 matrix instruction, exact 32-bit sums).
+//   Digits are signed bytes: unsigned digits of base_log <= 7, balanced ones of base_log <= 8.
+//   A key word is L(q) balanced base-256 limbs in [-128, 128) of its centred residue in (-q/2, q/2]; L limbs hold the values
+//   -128 (256^L - 1) / 255 .. 127 (256^L - 1) / 255, so L(q) is the smallest L with floor(q / 2) <= 127 (256^L - 1) / 255 (the
+//   negative side has one value to spare): 3 for q = 8380417, 8 for q = 2^60 - 2^14 + 1, at most 4 below 2^31 and 8 below 2^62.
+//   A product is at most 2^14 in magnitude, so a 32-bit sum takes LWE_MFMA_FLUSH_PRODUCTS = 2^16 of them (2^30) before it is
+//   folded into a 128-bit partial sum_l acc_l 2^(8 l), below 2^88; n_in * terms <= LWE_KS_MAX_SLOTS = 2^22 is 2^6 folds: the
+//   total is below 2^94 (2^61 on 32-bit lanes, L <= 4), and |total| <= 2^22 * 128 * q / 2 as a sum of digits times centred residues.
+//   The prepared key: limb planes in the matrix instruction's B-fragment order, [column tile of 16][K step of 64][limb][lane of 64][16 bytes],
+//   K = n_in * terms and the columns n_out + 1 padded to whole tiles with zero limbs.
+constexpr uint32_t LWE_MFMA_K_STEP = 64, LWE_MFMA_COL_TILE = 16, LWE_MFMA_FRAG_BYTES = 64 * 16;
+constexpr uint32_t LWE_MFMA_FLUSH_PRODUCTS = 1u << 16;
+static inline uint32_t lwe_mfma_limbs(uint64_t q) {
+  const unsigned __int128 half = q >> 1;
+  unsigned __int128 span = 1;                                    // (256^L - 1) / 255
+  uint32_t limbs = 1;
+  while (half > 127 * span) { span = span * 256 + 1; ++limbs; }
+  return limbs;
+}
+static constexpr size_t lwe_mfma_steps(size_t n_in, size_t terms) { return (n_in * terms + LWE_MFMA_K_STEP - 1) / LWE_MFMA_K_STEP; }
+static constexpr size_t lwe_mfma_col_tiles(size_t n_out) { return (n_out + 1 + LWE_MFMA_COL_TILE - 1) / LWE_MFMA_COL_TILE; }
+// at most 4097 * 65536 * 8 KiB: no step wraps size_t for arguments within check_lwe_ksk_prepare's limits
+static inline size_t lwe_mfma_prepared_bytes(uint64_t q, size_t n_in, size_t n_out, size_t terms) {
+  return lwe_mfma_col_tiles(n_out) * lwe_mfma_steps(n_in, terms) * lwe_mfma_limbs(q) * LWE_MFMA_FRAG_BYTES;
+}
+
 struct KernelPick { bool known, fused; int group, layout; };     // layout: CgLayout, cg_core.h (0 linear, 1 padded, 2 swizzled)
 // The kernel a variant names; TN_VARIANT_AUTO is the fused kernel where the plan has it (and no trace is wanted), else CG.
 static inline KernelPick pick_kernel(const ApiPlan& v, tn_variant variant, bool trace = false) {
@@ -127,6 +153,22 @@ struct __attribute__((visibility("hidden"))) ApiCheck {          // (hidden, sta
   bool lwe_sum(size_t n_in, size_t terms_) {
     return n_in * terms_ <= LWE_KS_MAX_SLOTS ||
            fail(TN_EUNSUPPORTED, "n_in * terms above 2^22 is not supported: a 128-bit sum holds 2^22 terms below 2^32 * 2^64");
+  }
+  // The prepared key switch (tn_lwe_ksk_prepared_bytes, tn_lwe_ksk_prepare_dev, tn_lwe_keyswitch_prepared_dev) under the same
+  // lwe_sum: its sum of signed digits (magnitude <= 128) times centred residues (magnitude <= q / 2) is |sum| <= 2^22 * 128 * q / 2,
+  // held as 32-bit sums of at most LWE_MFMA_FLUSH_PRODUCTS byte products folded into 128 bits (the bounds stand at the top of this file).
+  bool lwe_byte_digits(uint32_t base_log, uint32_t flags) {
+    return base_log <= ((flags & TN_GADGET_BALANCED) ? 8u : 7u) ||
+           fail(TN_EUNSUPPORTED, "digits wider than a signed byte are not supported (unsigned base_log <= 7, TN_GADGET_BALANCED base_log <= 8): "
+                                 "tn_lwe_keyswitch_dev is the route");
+  }
+  bool lwe_key_terms(size_t n_in, size_t terms_) {           // what gadget() asks of terms, without a base: 1 .. 64, n_in * terms key rows
+    if (!terms(terms_)) return false;
+    if (terms_ > 64) return fail(TN_EINVAL, "terms must be at most 64");
+    return rows(n_in, terms_, "n_in * terms", "key rows");
+  }
+  bool aligned16(const void* kprep) {                         // the kernel loads a lane's B fragment as one 16-byte word
+    return ((uintptr_t)kprep & 15u) == 0 || fail(TN_EINVAL, "kprep must be aligned to 16 bytes");
   }
   // byte ranges of buffers that are not rows of n words
   bool apart_bytes(const void* out, size_t out_bytes, const void* in, size_t in_bytes, const char* noun) {
@@ -266,6 +308,30 @@ static inline bool check_lwe_keyswitch(ApiCheck& k, const void* lwe, const void*
          k.rows(batch, n_out + 1, "batch * (n_out + 1)", "words") && k.work(batch) && k.buffers(lwe && ksk && out) &&
          k.apart_bytes(out, batch * (n_out + 1) * word, lwe, batch * (n_in + 1) * word, "an input") &&
          k.apart_bytes(out, batch * (n_out + 1) * word, ksk, n_in * terms * (n_out + 1) * word, "an input");
+}
+// tn_lwe_ksk_prepared_bytes (host only: no buffer but the answer's) and tn_lwe_ksk_prepare_dev: the plan, the two dimensions,
+// terms (1 .. 64, n_in * terms key rows), lwe_sum; then the answer's pointer, or the buffers, kprep's alignment and its byte
+// range (lwe_mfma_prepared_bytes) against the plain key's.  Every plan.  No batch: there is always work.
+static inline bool check_lwe_ksk_shape(ApiCheck& k, size_t n_in, size_t n_out, size_t terms) {
+  return k.plan() && k.lwe_dim(n_in, "n_in") && k.lwe_dim(n_out, "n_out") && k.lwe_key_terms(n_in, terms) && k.lwe_sum(n_in, terms);
+}
+static inline bool check_lwe_ksk_bytes(ApiCheck& k, size_t n_in, size_t n_out, size_t terms, const size_t* bytes) {
+  return check_lwe_ksk_shape(k, n_in, n_out, terms) && k.arguments(bytes != nullptr);
+}
+static inline bool check_lwe_ksk_prepare(ApiCheck& k, const void* ksk, const void* kprep, size_t n_in, size_t n_out, size_t terms) {
+  return check_lwe_ksk_shape(k, n_in, n_out, terms) && k.buffers(ksk && kprep) && k.aligned16(kprep) &&
+         k.apart_bytes(kprep, lwe_mfma_prepared_bytes(k.v.q, n_in, n_out, terms), ksk, n_in * terms * (n_out + 1) * (size_t)k.v.elem_bytes, "the input");
+}
+// tn_lwe_keyswitch_prepared_dev: check_lwe_keyswitch's list with the byte-wide digits behind lwe_digits' place, kprep's
+// alignment behind the buffers and kprep's byte range in place of ksk's.  Every plan.
+static inline bool check_lwe_keyswitch_prepared(ApiCheck& k, const void* lwe, const void* kprep, const void* out, size_t batch, size_t n_in,
+                                                size_t n_out, size_t terms, uint32_t base_log, uint32_t flags) {
+  const size_t word = (size_t)k.v.elem_bytes;
+  return k.plan() && k.lwe_dim(n_in, "n_in") && k.lwe_dim(n_out, "n_out") && k.gadget(n_in, terms, base_log, flags, "n_in * terms", "key rows") &&
+         k.lwe_byte_digits(base_log, flags) && k.lwe_sum(n_in, terms) && k.rows(batch, n_in + 1, "batch * (n_in + 1)", "words") &&
+         k.rows(batch, n_out + 1, "batch * (n_out + 1)", "words") && k.work(batch) && k.buffers(lwe && kprep && out) && k.aligned16(kprep) &&
+         k.apart_bytes(out, batch * (n_out + 1) * word, lwe, batch * (n_in + 1) * word, "an input") &&
+         k.apart_bytes(out, batch * (n_out + 1) * word, kprep, lwe_mfma_prepared_bytes(k.v.q, n_in, n_out, terms), "an input");
 }
 static inline bool check_pointwise(ApiCheck& k, const void* a, const void* b, const void* c, size_t batch) {      // in place is allowed
   return k.plan() && k.rows_wide(batch) && k.buffers(!batch || (a && b && c));

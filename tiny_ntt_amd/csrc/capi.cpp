@@ -366,6 +366,29 @@ extern "C" tn_status tn_lwe_keyswitch_dev(tn_plan* p, const void* lwe, const voi
   return TN_OK;
 }
 
+// ---- the key switch on the matrix cores: the key prepared as int8 limb planes, exact sums (every plan) -----------------------
+extern "C" tn_status tn_lwe_ksk_prepared_bytes(tn_plan* p, size_t n_in, size_t n_out, size_t terms, size_t* bytes) {
+  TN_CHECK("tn_lwe_ksk_prepared_bytes", check_lwe_ksk_bytes(k, n_in, n_out, terms, bytes));
+  *bytes = lwe_mfma_prepared_bytes(p->q, n_in, n_out, terms);
+  return TN_OK;
+}
+
+extern "C" tn_status tn_lwe_ksk_prepare_dev(tn_plan* p, const void* ksk, void* kprep, size_t n_in, size_t n_out, size_t terms, void* stream) {
+  TN_CHECK("tn_lwe_ksk_prepare_dev", check_lwe_ksk_prepare(k, ksk, kprep, n_in, n_out, terms));
+  TN_ON_DEVICE(p);
+  TN_HIP(launch_lwe_ksk_prepare(p, ksk, kprep, n_in, n_out, terms, pick_stream(p, stream)));
+  return TN_OK;
+}
+
+extern "C" tn_status tn_lwe_keyswitch_prepared_dev(tn_plan* p, const void* lwe, const void* kprep, void* out, size_t batch, size_t n_in, size_t n_out,
+                                                   size_t terms, uint32_t base_log, uint32_t flags, void* stream) {
+  TN_CHECK("tn_lwe_keyswitch_prepared_dev", check_lwe_keyswitch_prepared(k, lwe, kprep, out, batch, n_in, n_out, terms, base_log, flags));
+  TN_ON_DEVICE(p);
+  TN_HIP(launch_lwe_keyswitch_prepared(p, lwe, kprep, out, batch, n_in, n_out, terms, base_log, (flags & TN_GADGET_BALANCED) != 0,
+                                       pick_stream(p, stream)));
+  return TN_OK;
+}
+
 extern "C" tn_status tn_pointwise_mul_dev(tn_plan* p, const void* a, const void* b, void* c, size_t batch, void* stream) {
   TN_CHECK("tn_pointwise_mul_dev", check_pointwise(k, a, b, c, batch));
   TN_ON_DEVICE(p);

@@ -176,7 +176,8 @@ inline hipError_t launch_persistent(const tn_plan* p, hipStream_t s, const void*
 
 // kernels.hip (prepared operand: kernels_prepared.hip; transform domain: kernels_hat.hip; gadget: kernels_gadget.hip;
 // automorphisms: kernels_galois.hip; external product: kernels_extprod.hip; CMux rotation step: kernels_cmux.hip; blind rotation: kernels_blindrot.hip;
-// automorphism key switch: kernels_galoisks.hip; LWE modulus switch, sample extraction and key switch: kernels_lwe.hip)
+// automorphism key switch: kernels_galoisks.hip; LWE modulus switch, sample extraction and key switch: kernels_lwe.hip; the key
+// switch from a prepared key on the matrix cores: kernels_lwe_mfma.hip)
 bool fused_supported(u32 logn, int elem_bytes);
 const char* fused_kernel_name(const tn_plan* p);
 const char* cg_kernel_name(const tn_plan* p, int group, int layout);
@@ -233,6 +234,11 @@ hipError_t launch_lwe_modswitch(const tn_plan* p, const void* lwe, uint32_t* exp
 hipError_t launch_lwe_sample_extract(const tn_plan* p, const void* a, void* lwe, size_t batch, tn::u32 index, hipStream_t s);
 hipError_t launch_lwe_keyswitch(const tn_plan* p, const void* lwe, const void* ksk, void* out, size_t batch, size_t n_in, size_t n_out, size_t terms,
                                 tn::u32 base_log, bool balanced, hipStream_t s);
+// the key switch on the matrix cores (kernels_lwe_mfma.hip; every plan).  tn_lwe_ksk_prepare_dev: ksk -> kprep, int8 limb planes in
+// B-fragment order (lwe_mfma_core.h).  tn_lwe_keyswitch_prepared_dev: out as launch_lwe_keyswitch writes it, from kprep
+hipError_t launch_lwe_ksk_prepare(const tn_plan* p, const void* ksk, void* kprep, size_t n_in, size_t n_out, size_t terms, hipStream_t s);
+hipError_t launch_lwe_keyswitch_prepared(const tn_plan* p, const void* lwe, const void* kprep, void* out, size_t batch, size_t n_in, size_t n_out,
+                                         size_t terms, tn::u32 base_log, bool balanced, hipStream_t s);
 hipError_t launch_cg(const tn_plan* p, int mode, int group, int layout, const void* a, const void* b, void* out,
                      void* trace, size_t batch, hipStream_t s);
 hipError_t launch_pointwise(const tn_plan* p, const void* a, const void* b, void* c, size_t batch, hipStream_t s);

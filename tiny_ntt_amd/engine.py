@@ -47,6 +47,7 @@ EXPORTED_SYMBOLS = (
     "tn_monomial_mul_dev", "tn_poly_cmux_rotate_prepared_dev", "tn_poly_blind_rotate_prepared_dev",
     "tn_automorphism_dev", "tn_automorphism_prepared_dev", "tn_poly_galois_keyswitch_prepared_dev",
     "tn_lwe_modswitch_dev", "tn_sample_extract_dev", "tn_lwe_keyswitch_dev",
+    "tn_lwe_ksk_prepared_bytes", "tn_lwe_ksk_prepare_dev", "tn_lwe_keyswitch_prepared_dev",
     "tn_plan_export_table", "tn_ntt_forward_dev", "tn_ntt_inverse_dev",
     "tn_ntt_forward_host", "tn_ntt_inverse_host", "tn_ntt_forward_trace_host", "tn_twisted_ntt_forward_dev",
     "tn_twisted_ntt_forward_host", "tn_schoolbook_host",
@@ -117,6 +118,9 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.tn_lwe_modswitch_dev.argtypes = [vp, vp, vp, sz, sz, vp]
     lib.tn_sample_extract_dev.argtypes = [vp, vp, vp, sz, u32, vp]
     lib.tn_lwe_keyswitch_dev.argtypes = [vp, vp, vp, vp, sz, sz, sz, sz, u32, u32, vp]
+    lib.tn_lwe_ksk_prepared_bytes.argtypes = [vp, sz, sz, sz, ctypes.POINTER(sz)]
+    lib.tn_lwe_ksk_prepare_dev.argtypes = [vp, vp, vp, sz, sz, sz, vp]
+    lib.tn_lwe_keyswitch_prepared_dev.argtypes = [vp, vp, vp, vp, sz, sz, sz, sz, u32, u32, vp]
     lib.tn_schoolbook_dev.argtypes = [vp, vp, vp, vp, sz, vp]
     lib.tn_plan_export_table.argtypes = [vp, ci, vp]
     for name in ("tn_ntt_forward_dev", "tn_ntt_inverse_dev", "tn_twisted_ntt_forward_dev"):
@@ -182,6 +186,14 @@ class PreparedOperand:
 
     def __init__(self, plan, tensor, rows: int):
         self.plan, self.tensor, self.rows = plan, tensor, int(rows)
+
+
+class PreparedLweKey:
+    """An LWE key-switch key prepared once (Plan.lwe_ksk_prepare) for any number of Plan.lwe_keyswitch_prepared calls: opaque
+    device bytes (include/tinyntt.h: tn_lwe_ksk_prepare_dev), valid only with the plan that made them."""
+
+    def __init__(self, plan, tensor, n_in: int, n_out: int, terms: int):
+        self.plan, self.tensor, self.n_in, self.n_out, self.terms = plan, tensor, int(n_in), int(n_out), int(terms)
 
 
 class Plan:
@@ -821,6 +833,51 @@ class Plan:
                                                          GADGET_BALANCED if balanced else 0, self._stream_ptr(stream)))
         return self._result(c, host, one, out)
 
+    def lwe_ksk_prepared_bytes(self, n_in, n_out, terms):
+        """The size in bytes of the prepared form of a key (n_in, terms, n_out + 1), padding included (tn_lwe_ksk_prepared_bytes)."""
+        size = ctypes.c_size_t(0)
+        _check(self._lib, self._lib.tn_lwe_ksk_prepared_bytes(self._h, int(n_in), int(n_out), int(terms), ctypes.byref(size)))
+        return int(size.value)
+
+    def lwe_ksk_prepare(self, ksk, terms, stream=None) -> PreparedLweKey:
+        """Prepare an LWE key-switch key for the matrix cores (tn_lwe_ksk_prepare_dev): ksk is (n_in, terms, n_out + 1) words of
+        the plan's type, host values or a device tensor of that shape (a plain key, as Plan.lwe_keyswitch takes it).  Returns a
+        PreparedLweKey: signed-byte limbs of the centred residues in the matrix instruction's operand order, opaque, for
+        Plan.lwe_keyswitch_prepared and Plan.bootstrap of THIS plan.  Works on every plan."""
+        import torch
+        terms = int(terms)
+        shape = tuple(ksk.shape) if _is_torch(ksk) else np.shape(ksk)
+        if len(shape) != 3 or shape[1] != terms or shape[2] < 2:
+            raise ValueError(f"Expected a key of shape (n_in, {terms}, n_out + 1), got {tuple(shape)}")
+        n_in, n_out = int(shape[0]), int(shape[2]) - 1
+        if _is_torch(ksk):
+            k = ksk
+            if not k.is_cuda or k.element_size() != self.elem_bytes or not k.is_contiguous():
+                raise TinyNttError(TN_EINVAL, f"ksk: need a contiguous device tensor of {self.elem_bytes}-byte integers")
+        else:
+            k, _, _ = self._lwe_in(np.asarray(ksk).reshape(-1, n_out + 1), "ksk", n_out + 1)
+        prep = torch.empty(self.lwe_ksk_prepared_bytes(n_in, n_out, terms), dtype=torch.int8, device=k.device)
+        _check(self._lib, self._lib.tn_lwe_ksk_prepare_dev(self._h, k.data_ptr(), prep.data_ptr(), n_in, n_out, terms, self._stream_ptr(stream)))
+        return PreparedLweKey(self, prep, n_in, n_out, terms)
+
+    def lwe_keyswitch_prepared(self, lwe, key: PreparedLweKey, base_log, balanced=False, out=None, stream=None):
+        """Plan.lwe_keyswitch from a prepared key (tn_lwe_keyswitch_prepared_dev), bit for bit the same rows: lwe is
+        (batch, key.n_in + 1), or one row, host values or a device tensor; returns (batch, key.n_out + 1).  Digits must fit a signed
+        byte: base_log <= 7, or <= 8 with balanced digits; wider ones are Plan.lwe_keyswitch's.  Works on every plan."""
+        if not isinstance(key, PreparedLweKey):
+            raise TypeError("lwe_keyswitch_prepared: the key must come from Plan.lwe_ksk_prepare")
+        if key.plan is not self:
+            raise TinyNttError(TN_EINVAL, "lwe_keyswitch_prepared: the prepared key belongs to another plan")
+        x, host, one = self._lwe_in(lwe, "lwe", key.n_in + 1)
+        batch = int(x.shape[0])
+        if key.tensor.numel() * key.tensor.element_size() < self.lwe_ksk_prepared_bytes(key.n_in, key.n_out, key.terms):
+            raise TinyNttError(TN_EINVAL, "lwe_keyswitch_prepared: the prepared key is shorter than tn_lwe_ksk_prepared_bytes")
+        c = self._lwe_out(out, (batch, key.n_out + 1), x.device)
+        _check(self._lib, self._lib.tn_lwe_keyswitch_prepared_dev(self._h, x.data_ptr(), key.tensor.data_ptr(), c.data_ptr(), batch, key.n_in, key.n_out,
+                                                                  key.terms, int(base_log), GADGET_BALANCED if balanced else 0,
+                                                                  self._stream_ptr(stream)))
+        return self._result(c, host, one, out)
+
     def bootstrap(self, lwe, bsk: PreparedOperand, test_vector, ksk, *, terms, base_log, ks_terms, ks_base_log, balanced=False, ks_balanced=False,
                   one_launch=False, stream=None):
         """A programmable bootstrap of LWE ciphertexts, LWE in and LWE under the same key out, from the library's calls alone:
@@ -829,7 +886,8 @@ class Plan:
           3. poly_blind_rotate_prepared when one_launch is set, else blind_rotate, over exps[:dim] with the bootstrap key bsk
              (dim * 4 * terms prepared rows: RGSW encryptions of the key bits, one per step);
           4. sample_extract at index 0: LWE of dimension n under the coefficients of the ring key;
-          5. lwe_keyswitch with ksk (n, ks_terms, dim + 1) back to dimension dim.
+          5. lwe_keyswitch with ksk (n, ks_terms, dim + 1) back to dimension dim; where ksk is a PreparedLweKey (lwe_ksk_prepare),
+             lwe_keyswitch_prepared with it: the same rows from the matrix cores (ks_base_log within its byte-wide digits).
         lwe is (batch, dim + 1), host values or a device tensor; test_vector one polynomial of n words, host or device; ksk host
         or device words.  The two blind-rotation routes are bit-identical.  Which suits which batch (README, "Blind rotation"): one
         launch keeps the accumulator on chip and wins where the batch leaves workgroups to spare; the step-by-step loop reads
@@ -864,7 +922,12 @@ class Plan:
         else:
             acc = self.blind_rotate(acc, exps[:dim], bsk, terms, base_log, balanced, stream=stream)
         big = self.sample_extract(acc, 0, stream=stream)
-        c = self.lwe_keyswitch(big, ksk, dim, ks_terms, ks_base_log, ks_balanced, stream=stream)
+        if isinstance(ksk, PreparedLweKey):
+            if (ksk.n_in, ksk.n_out, ksk.terms) != (self.n, dim, int(ks_terms)):
+                raise ValueError(f"Expected a prepared key of shape ({self.n}, {int(ks_terms)}, {dim + 1}), got ({ksk.n_in}, {ksk.terms}, {ksk.n_out + 1})")
+            c = self.lwe_keyswitch_prepared(big, ksk, ks_base_log, ks_balanced, stream=stream)
+        else:
+            c = self.lwe_keyswitch(big, ksk, dim, ks_terms, ks_base_log, ks_balanced, stream=stream)
         return self._result(c, host, one)
 
     # ---- ring automorphisms a(x) -> a(x^g) ----------------------------------------
