@@ -595,6 +595,51 @@ tn_status tn_poly_galois_keyswitch_prepared_dev(tn_plan *plan, const void *a, ui
                                                 void *c, size_t batch, size_t terms, uint32_t base_log, uint32_t flags, void *stream);
 
 /*
+ * PACK STEP AND TRACE STEP: one level of LWE -> RLWE ring packing (PackLWEs and the field trace of Chen, Dai, Kim, Song,
+ * "Efficient Homomorphic Conversion Between (Ring) LWE Ciphertexts"), from ONE launch:
+ *     ct = (ev + X^rot od) + EvalAuto(ev - X^rot od, g),
+ * EvalAuto the homomorphic automorphism above.  With t = X^rot * od on both components, s = ev + t and d = ev - t (every input
+ * word taken mod q):
+ *     c[r][0] = ( s0 + sigma_g(d0) + sum_{j < terms} digit_j( sigma_g(d1) ) * b[k][0][j] ) mod q
+ *     c[r][1] = ( s1 +               sum_{j < terms} digit_j( sigma_g(d1) ) * b[k][1][j] ) mod q,
+ * k = (bhat_sets == 1 ? 0 : r), r < batch.  ev, od and c are [batch][2][n]; bhat is [bhat_sets][2][terms][n] prepared rows, the
+ * key from sigma_g(s) to s in the layout of tn_poly_galois_keyswitch_prepared_dev; rot (below 2n) and galois (odd, below 2n) are
+ * passed by value: no table, and a captured launch replays the values it was captured with.  od == NULL is the TRACE STEP,
+ * ct = ev + EvalAuto(ev, g) (s = d = ev); rot must then be 0.
+ * The result is BIT-IDENTICAL to the explicit route: tn_monomial_mul_dev on od with the exponent rot; s and d by addition and
+ * subtraction mod q of canonical words; tn_poly_galois_keyswitch_prepared_dev on d; the addition of s mod q.  The subtraction
+ * comes before sigma_g and sigma_g before the digits are cut.  terms + 2 transforms per row, as in the automorphism key switch.
+ * c must not overlap ev, od or bhat (byte ranges): the kernel reads a row's inputs again after its first component is stored.
+ * Both indices into a row are masked: no value of rot or galois could cause an out-of-bounds access.
+ *
+ * The packing tree (Plan.pack_lwes in the Python package has it whole): embed ell = 2^m LWE ciphertexts with tn_lwe_embed_dev
+ * at index 0, slot-major; at level t = 1 .. m pair the first half of the list with the second in one launch with
+ * rot = n / 2^t, g = 2^t + 1; then trace steps for t = m + 1 .. log2 n with g = 2^t + 1.  The phase of the result is
+ * n * sum_j mu_j X^(j n / ell) plus noise: THE FACTOR n IS NOT REMOVED.  The caller scales by n^-1 mod q beforehand, as the paper does.
+ *
+ * Status, in this order: TN_EINVAL for a NULL plan; TN_EUNSUPPORTED for a plan without the fused kernels; TN_EINVAL for a galois
+ * that is even or >= 2n; for rot >= 2n, or rot != 0 with od == NULL; for everything the gadget calls refuse (as
+ * tn_poly_galois_keyswitch_prepared_dev); batch == 0 succeeds and launches nothing; TN_EINVAL for a NULL ev, bhat or c, for
+ * bhat_sets neither 1 nor batch, and for c's batch * 2 rows overlapping ev's or od's batch * 2 rows or bhat's bhat_sets * 2 * terms rows.
+ * The call enqueues on the stream and returns, and may be stream-captured.  Fused plans only.  The reference has no counterpart.
+ *
+ * When to use which (MI355X, profiles/pack_ab.txt, tools/gpu_pack.py; one process per point, 9 interleaved repeats, one shared key,
+ * balanced digits, terms 2 - 4, (g, rot) in {(3, n/2), (5, n/4), one seeded pair}, outputs compared in full first; n = 4096 / 60-bit,
+ * 65,536 rows and n = 1024 / 24-bit, 4,096 rows; the README has the table):
+ *   - a pack level: the one launch is faster than the explicit route, its three torch passes included, at all six points and for every g
+ *     by disjoint ranges, x 0.21 - 0.27 at n = 4096 (5,667 - 5,684 against 26,868 - 26,903 us at two terms) and x 0.25 - 0.32 at
+ *     n = 1024 (53.5 - 53.7 against 216.0 - 216.3 us), and faster than the route's two launches alone, x 0.90 - 0.94, at all six.
+ *   - against a plain tn_poly_galois_keyswitch_prepared_dev on the same rows it is SLOWER at all six by disjoint ranges, x 1.18 - 1.26
+ *     at n = 4096 and x 1.11 - 1.16 at n = 1024: the second input ciphertext, read twice, and the sums.
+ *   - a trace step (od == NULL): x 0.41 - 0.56 of its route (the key switch and one torch addition) at all six by disjoint ranges;
+ *     x 1.03 - 1.05 of the plain key switch at n = 4096 (disjoint), x 1.01 - 1.03 at n = 1024 (within the spread at three and four terms).
+ *   - not measured: n = 256, n = 8192, a key per row, unsigned digits, the canonical policy.
+ */
+tn_status tn_poly_pack_step_prepared_dev(tn_plan *plan, const void *ev, const void *od, uint32_t rot, uint32_t galois, const void *bhat,
+                                         size_t bhat_sets, void *c, size_t batch, size_t terms, uint32_t base_log, uint32_t flags,
+                                         void *stream);
+
+/*
  * THE LWE ENDS OF A PROGRAMMABLE BOOTSTRAP: the modulus switch that turns an LWE ciphertext into the exponents of a blind
  * rotation (tn_lwe_modswitch_dev), the sample extraction that takes an LWE ciphertext out of the rotated accumulator
  * (tn_sample_extract_dev) and the LWE-to-LWE key switch back to the small key (tn_lwe_keyswitch_dev).  With tn_monomial_mul_dev
@@ -663,6 +708,16 @@ tn_status tn_poly_galois_keyswitch_prepared_dev(tn_plan *plan, const void *a, ui
 #define TN_LWE_MAX_DIM 65536
 tn_status tn_lwe_modswitch_dev(tn_plan *plan, const void *lwe, uint32_t *exps, size_t batch, size_t dim, void *stream);
 tn_status tn_sample_extract_dev(tn_plan *plan, const void *a, void *lwe, size_t batch, uint32_t index, void *stream);
+/*
+ * tn_lwe_embed_dev: the exact inverse of tn_sample_extract_dev at `index` (below n): lwe is [batch][n + 1], a is [batch][2][n],
+ *     a[r][1][k] = lwe[r][index - k] mod q                      for k <= index,
+ *     a[r][1][k] = (q - lwe[r][n + index - k] mod q) mod q      for index < k < n   (a zero stays 0),
+ *     a[r][0][index] = lwe[r][n] mod q, a[r][0][k] = 0 elsewhere.
+ * Coefficient `index` of the phase of a[r] is the phase of lwe[r] under the coefficients of s (the other coefficients are not
+ * zero: a trace removes them).  Every plan; status as tn_sample_extract_dev with the two buffers in each other's place; the
+ * index into the row is masked besides.  Enqueues and returns, does not allocate, may be stream-captured.
+ */
+tn_status tn_lwe_embed_dev(tn_plan *plan, const void *lwe, void *a, size_t batch, uint32_t index, void *stream);
 tn_status tn_lwe_keyswitch_dev(tn_plan *plan, const void *lwe, const void *ksk, void *out, size_t batch, size_t n_in, size_t n_out,
                                size_t terms, uint32_t base_log, uint32_t flags, void *stream);
 

@@ -132,6 +132,11 @@ struct __attribute__((visibility("hidden"))) ApiCheck {          // (hidden, sta
         return fail(TN_EINVAL, ("galois[" + std::to_string(m) + "] = " + std::to_string(g[m]) + " is not an odd element below 2n").c_str());
     return true;
   }
+  // The rotation of tn_poly_pack_step_prepared_dev: below 2n; the trace step (no od) has nothing to rotate
+  bool pack_rot(uint32_t rot, bool has_od) {
+    if (rot >= 2 * (uint64_t)v.n) return fail(TN_EINVAL, ("rot = " + std::to_string(rot) + " is not below 2n").c_str());
+    return has_od || rot == 0 || fail(TN_EINVAL, "rot must be 0 when od is NULL (the trace step)");
+  }
   // The byte ranges of out_rows rows at out and in_rows rows at in share no byte: the kernels prefetch the next row's input
   // while a row's result is being stored.  Compared as integers: a caller may pass any address, also one near 0.
   bool apart(const void* out, size_t out_rows, const void* in, size_t in_rows, const char* noun) {
@@ -286,6 +291,22 @@ static inline bool check_galois_keyswitch(ApiCheck& k, const void* a, uint32_t g
   return k.plan() && k.fused() && k.galois(&galois, 1) && k.gadget(rows_times(batch, 2), terms, base_log, flags, "batch * 2 * terms") &&
          k.work(batch) && k.buffers(a && bhat && c) && k.sets(sets, batch, "bhat_sets", "one set of operands for every row") &&
          k.apart(c, batch * 2, a, batch * 2, "an input") && k.apart(c, batch * 2, bhat, sets * 2 * terms, "an input");
+}
+// tn_poly_pack_step_prepared_dev: check_galois_keyswitch's list with the rotation behind the element (rot below 2n; the
+// trace step, od == NULL, takes rot == 0 only) and two inputs of batch * 2 rows; od is not among the buffers that must be
+// present.  The kernel reads a row's inputs again after its first component is stored, so nothing runs in place.
+static inline bool check_pack_step(ApiCheck& k, const void* ev, const void* od, uint32_t rot, uint32_t galois, const void* bhat, size_t sets,
+                                   const void* c, size_t batch, size_t terms, uint32_t base_log, uint32_t flags) {
+  return k.plan() && k.fused() && k.galois(&galois, 1) && k.pack_rot(rot, od != nullptr) &&
+         k.gadget(rows_times(batch, 2), terms, base_log, flags, "batch * 2 * terms") && k.work(batch) && k.buffers(ev && bhat && c) &&
+         k.sets(sets, batch, "bhat_sets", "one set of operands for every row") && k.apart(c, batch * 2, ev, batch * 2, "an input") &&
+         (!od || k.apart(c, batch * 2, od, batch * 2, "an input")) && k.apart(c, batch * 2, bhat, sets * 2 * terms, "an input");
+}
+// tn_lwe_embed_dev: check_sample_extract's list with the two buffers in each other's place.  Every plan.
+static inline bool check_lwe_embed(ApiCheck& k, const void* lwe, const void* a, size_t batch, uint32_t index) {
+  const size_t word = (size_t)k.v.elem_bytes;
+  return k.plan() && k.lwe_index(index) && k.rows(batch, (size_t)k.v.n + 1, "batch * (n + 1)", "words") && k.work(batch) && k.buffers(a && lwe) &&
+         k.apart_bytes(a, batch * 2 * (size_t)k.v.n * word, lwe, batch * ((size_t)k.v.n + 1) * word, "the input");
 }
 // tn_lwe_modswitch_dev: lwe has batch * (dim + 1) words of the plan's type, exps as many 32-bit words.  Every plan.
 static inline bool check_lwe_modswitch(ApiCheck& k, const void* lwe, const void* exps, size_t batch, size_t dim) {

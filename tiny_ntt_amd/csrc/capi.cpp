@@ -318,6 +318,17 @@ extern "C" tn_status tn_poly_galois_keyswitch_prepared_dev(tn_plan* p, const voi
   return TN_OK;
 }
 
+// ---- one level of the LWE -> RLWE packing tree, or one trace step (od == NULL), from one launch ----------------------------
+extern "C" tn_status tn_poly_pack_step_prepared_dev(tn_plan* p, const void* ev, const void* od, uint32_t rot, uint32_t galois, const void* bhat,
+                                                    size_t bhat_sets, void* c, size_t batch, size_t terms, uint32_t base_log, uint32_t flags,
+                                                    void* stream) {
+  TN_CHECK("tn_poly_pack_step_prepared_dev", check_pack_step(k, ev, od, rot, galois, bhat, bhat_sets, c, batch, terms, base_log, flags));
+  TN_ON_DEVICE(p);
+  TN_HIP(launch_polydot_pack(p, ev, od, rot, galois, bhat, bhat_sets == 1, c, batch, terms, base_log, (flags & TN_GADGET_BALANCED) != 0,
+                             pick_stream(p, stream)));
+  return TN_OK;
+}
+
 // ---- blind rotation: `steps` CMux rotation steps from one launch, the accumulator in LDS across them ------------------------
 extern "C" tn_status tn_poly_blind_rotate_prepared_dev(tn_plan* p, const void* a, const uint32_t* exps, const void* bhat, void* c, size_t batch,
                                                        size_t comps, size_t steps, size_t terms, uint32_t base_log, uint32_t flags, void* stream) {
@@ -355,6 +366,13 @@ extern "C" tn_status tn_sample_extract_dev(tn_plan* p, const void* a, void* lwe,
   TN_CHECK("tn_sample_extract_dev", check_sample_extract(k, a, lwe, batch, index));
   TN_ON_DEVICE(p);
   TN_HIP(launch_lwe_sample_extract(p, a, lwe, batch, index, pick_stream(p, stream)));
+  return TN_OK;
+}
+
+extern "C" tn_status tn_lwe_embed_dev(tn_plan* p, const void* lwe, void* a, size_t batch, uint32_t index, void* stream) {
+  TN_CHECK("tn_lwe_embed_dev", check_lwe_embed(k, lwe, a, batch, index));
+  TN_ON_DEVICE(p);
+  TN_HIP(launch_lwe_embed(p, lwe, a, batch, index, pick_stream(p, stream)));
   return TN_OK;
 }
 

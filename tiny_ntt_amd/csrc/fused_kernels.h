@@ -257,6 +257,15 @@ __device__ __forceinline__ E ld_operand(const E* __restrict__ p, u32 row, u32 ta
 #endif
 }
 
+// Word (v mod n) of row `row` of p: the load of a row rotated by a monomial (kernels_cmux.hip, kernels_pack.hip; cmux_core.h's
+// monomial_index).  The index is MASKED to the row: no v addresses a word outside it.  A plain load: the row is read again by
+// the unit-stride load and may hit in L2.
+template <typename E, typename Cfg>
+__device__ __forceinline__ E ld_rotated(const E* __restrict__ p, u32 row, u32 v) {
+  const TN_GLOBAL_AS E* rp = uniform_ptr(p + ((size_t)row << Cfg::LOGN));
+  return rp[v & (u32)(Cfg::N - 1)];
+}
+
 template <typename E, typename Cfg>
 __device__ __forceinline__ void st_result(E* __restrict__ c, u32 row, u32 tau, const E (&x)[Cfg::R]) {
 #if TN_ABL_ROWMASK

@@ -75,12 +75,6 @@ hipError_t launch_monomial_mul(const tn_plan* p, const void* a, const uint32_t* 
 // position of the barrier, two inverses and two stores.  2 * terms + 2 transforms per output row.
 // No address depends on data except through the masked exponent: the rotated index is taken & (n - 1) of the row the own
 // words come from, whatever exps holds.
-template <typename E, typename Cfg>
-__device__ __forceinline__ E ld_rotated(const E* __restrict__ p, u32 row, u32 v) {
-  const TN_GLOBAL_AS E* rp = uniform_ptr(p + ((size_t)row << Cfg::LOGN));
-  return rp[monomial_index(v, Cfg::LOGN)];
-}
-
 template <typename E, int LOGN, int LPT, bool LAZY, bool BC, bool SHARED, int XL>
 __global__ void __launch_bounds__((1 << (LOGN - LPT)), (dot_waves<E, LOGN, LPT, LAZY>()))
 polydot_cmux_kernel(const Arith<E> ar, const typename TwOf<E>::type* __restrict__ tab_fwd, const typename TwOf<E>::type* __restrict__ tab_inv,

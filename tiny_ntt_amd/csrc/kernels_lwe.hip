@@ -40,6 +40,13 @@ lwe_sample_extract_kernel(const Arith<E> ar, const E* __restrict__ a, E* __restr
   }
 }
 
+// lwe [batch][n + 1] -> a [batch][2][n]: the extraction's inverse, element-wise at a grid stride (lwe_embed_words).
+template <typename E>
+__global__ void __launch_bounds__(LWE_THREADS)
+lwe_embed_kernel(const Arith<E> ar, const E* __restrict__ lwe, E* __restrict__ a, u32 batch, u32 logn, u32 index) {
+  lwe_embed_words<E>(lwe, a, batch, logn, index, (size_t)blockIdx.x * LWE_THREADS + threadIdx.x, (size_t)gridDim.x * LWE_THREADS, ar);
+}
+
 // A tile of LWE_KS_ROWS rows by LWE_KS_COLS columns per pass of the loop, a thread per column with LWE_KS_ROWS 128-bit sums;
 // the input words go through the digit slab chunk by chunk.  Threads past column n_out cut digits and keep the barriers.
 template <typename E, bool BAL>
@@ -100,6 +107,18 @@ static hipError_t launch_lwe_sample_extract_t(const tn_plan* p, const void* a, v
 hipError_t launch_lwe_sample_extract(const tn_plan* p, const void* a, void* lwe, size_t batch, u32 index, hipStream_t s) {
   if (batch == 0) return hipSuccess;
   return p->elem_bytes == 8 ? launch_lwe_sample_extract_t<u64>(p, a, lwe, batch, index, s) : launch_lwe_sample_extract_t<u32>(p, a, lwe, batch, index, s);
+}
+
+template <typename E>
+static hipError_t launch_lwe_embed_t(const tn_plan* p, const void* lwe, void* a, size_t batch, u32 index, hipStream_t s) {
+  const size_t words = (batch * 2) << p->logn;                          // below 2^32 (check_lwe_embed)
+  const u32 grid = lwe_grid(p, (words + LWE_THREADS - 1) / LWE_THREADS, 8);
+  hipLaunchKernelGGL(lwe_embed_kernel<E>, dim3(grid), dim3(LWE_THREADS), 0, s, plan_arith<E>(p), (const E*)lwe, (E*)a, (u32)batch, p->logn, index);
+  return hipGetLastError();
+}
+hipError_t launch_lwe_embed(const tn_plan* p, const void* lwe, void* a, size_t batch, u32 index, hipStream_t s) {
+  if (batch == 0) return hipSuccess;
+  return p->elem_bytes == 8 ? launch_lwe_embed_t<u64>(p, lwe, a, batch, index, s) : launch_lwe_embed_t<u32>(p, lwe, a, batch, index, s);
 }
 
 template <typename E, bool BAL>

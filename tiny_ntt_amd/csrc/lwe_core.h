@@ -94,6 +94,31 @@ TN_HD void lwe_extract_gather(const E* __restrict__ a, const E* img, E* __restri
   }
 }
 
+// ---- embedding --------------------------------------------------------------------------------------------------
+// lwe [batch][n + 1] -> a [batch][2][n], the inverse of the extraction at `index`: a[1][k] = lwe[index - k] for k <= index,
+// -lwe[n + index - k] above it; a[0][index] = lwe[n], 0 elsewhere.  Element-wise: thread `first` of `stride` takes output
+// words first, first + stride, ... below batch * 2n (below 2^32: check_lwe_embed) and stores them at unit stride; a wave's
+// loads run backwards over consecutive words (the same cache lines).  The index into the row is MASKED, as the extraction's.
+template <typename E>
+TN_HD void lwe_embed_words(const E* __restrict__ lwe, E* __restrict__ a, u32 batch, u32 logn, u32 index, size_t first, size_t stride, const Arith<E>& ar) {
+  const u32 n = 1u << logn, n1 = n - 1u;
+  index &= n1;
+  const size_t total = ((size_t)batch * 2) << logn;
+  for (size_t j = first; j < total; j += stride) {
+    const size_t r = j >> (logn + 1);
+    const u32 k = (u32)j & n1;
+    const E* row = lwe + r * ((size_t)n + 1);
+    E v;
+    if (((j >> logn) & 1u) == 0) {
+      v = k == index ? lwe_canon(row[n], ar) : (E)0;
+    } else {
+      const E x = lwe_canon(galois_ld(row + ((index - k) & n1)), ar);
+      v = k > index ? galois_neg(x, ar.q) : x;
+    }
+    galois_st(a + j, v);
+  }
+}
+
 // ---- key switch -------------------------------------------------------------------------------------------------
 // out[r][k] = ( [k == n_out] b_r + sum_{i < n_in} sum_{j < terms} d_j(a_r[i]) ksk[i][j][k] ) mod q: a product
 // [batch][n_in terms] x [n_in terms][n_out + 1] with small left factors.  A workgroup owns a tile of LWE_KS_ROWS batch rows by

@@ -176,7 +176,7 @@ inline hipError_t launch_persistent(const tn_plan* p, hipStream_t s, const void*
 
 // kernels.hip (prepared operand: kernels_prepared.hip; transform domain: kernels_hat.hip; gadget: kernels_gadget.hip;
 // automorphisms: kernels_galois.hip; external product: kernels_extprod.hip; CMux rotation step: kernels_cmux.hip; blind rotation: kernels_blindrot.hip;
-// automorphism key switch: kernels_galoisks.hip; LWE modulus switch, sample extraction and key switch: kernels_lwe.hip; the key
+// automorphism key switch: kernels_galoisks.hip; pack / trace step: kernels_pack.hip; LWE modulus switch, sample extraction, embedding and key switch: kernels_lwe.hip; the key
 // switch from a prepared key on the matrix cores: kernels_lwe_mfma.hip)
 bool fused_supported(u32 logn, int elem_bytes);
 const char* fused_kernel_name(const tn_plan* p);
@@ -222,6 +222,11 @@ hipError_t launch_polydot_blindrot(const tn_plan* p, const void* a, const uint32
 // c[r][o] = [o == 0] sigma_g(a[r][0]) + sum_j digit_j(sigma_g(a[r][1])) * b[shared ? 0 : r][o][j], o < 2; galois odd, below 2n
 hipError_t launch_polydot_galoisks(const tn_plan* p, const void* a, uint32_t galois, const void* bhat, bool shared, void* c, size_t batch, size_t terms,
                                    tn::u32 base_log, bool balanced, hipStream_t s);
+// pack / trace step (kernels_pack.hip; tn_poly_pack_step_prepared_dev, fused plans only): ev, od, c [batch][2][n]; with
+// t = X^rot od (od == NULL: t = 0), s = ev + t, d = ev - t: c[r][o] = s[o] + [o == 0] sigma_g(d[0]) + sum_j digit_j(sigma_g(d[1])) *
+// b[shared ? 0 : r][o][j], o < 2; rot below 2n, galois odd and below 2n
+hipError_t launch_polydot_pack(const tn_plan* p, const void* ev, const void* od, uint32_t rot, uint32_t galois, const void* bhat, bool shared, void* c,
+                               size_t batch, size_t terms, tn::u32 base_log, bool balanced, hipStream_t s);
 // ring automorphisms a(x) -> a(x^g) (kernels_galois.hip): count images of every row, out[r][m] = sigma_{galois[m]}(row r); on
 // coefficient rows (tn_automorphism_dev: every plan) and on prepared rows (tn_automorphism_prepared_dev: fused plans only)
 hipError_t launch_automorphism(const tn_plan* p, const void* a, void* out, size_t batch, const uint32_t* galois, size_t count, hipStream_t s);
@@ -232,6 +237,8 @@ hipError_t launch_automorphism_prepared(const tn_plan* p, const void* xhat, void
 // phase.  tn_lwe_keyswitch_dev: out[r][k] = [k == n_out] b_r + sum_i sum_j digit_j(a_r[i]) * ksk[i][j][k], ksk [n_in][terms][n_out + 1]
 hipError_t launch_lwe_modswitch(const tn_plan* p, const void* lwe, uint32_t* exps, size_t batch, size_t dim, hipStream_t s);
 hipError_t launch_lwe_sample_extract(const tn_plan* p, const void* a, void* lwe, size_t batch, tn::u32 index, hipStream_t s);
+// tn_lwe_embed_dev: lwe [batch][n + 1] -> a [batch][2][n], the inverse of the extraction at `index`
+hipError_t launch_lwe_embed(const tn_plan* p, const void* lwe, void* a, size_t batch, tn::u32 index, hipStream_t s);
 hipError_t launch_lwe_keyswitch(const tn_plan* p, const void* lwe, const void* ksk, void* out, size_t batch, size_t n_in, size_t n_out, size_t terms,
                                 tn::u32 base_log, bool balanced, hipStream_t s);
 // the key switch on the matrix cores (kernels_lwe_mfma.hip; every plan).  tn_lwe_ksk_prepare_dev: ksk -> kprep, int8 limb planes in

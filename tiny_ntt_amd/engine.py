@@ -19,6 +19,8 @@ from typing import Optional
 
 import numpy as np
 
+from . import numtheory
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TINYNTT_LIB") or os.path.join(_HERE, "lib", "libtinyntt.so")   # env override: developer A/B builds
 
@@ -45,8 +47,8 @@ EXPORTED_SYMBOLS = (
     "tn_gadget_decompose_dev", "tn_poly_gadget_dot_prepared_dev", "tn_poly_gadget_multidot_prepared_dev",
     "tn_poly_external_product_prepared_dev",
     "tn_monomial_mul_dev", "tn_poly_cmux_rotate_prepared_dev", "tn_poly_blind_rotate_prepared_dev",
-    "tn_automorphism_dev", "tn_automorphism_prepared_dev", "tn_poly_galois_keyswitch_prepared_dev",
-    "tn_lwe_modswitch_dev", "tn_sample_extract_dev", "tn_lwe_keyswitch_dev",
+    "tn_automorphism_dev", "tn_automorphism_prepared_dev", "tn_poly_galois_keyswitch_prepared_dev", "tn_poly_pack_step_prepared_dev",
+    "tn_lwe_modswitch_dev", "tn_sample_extract_dev", "tn_lwe_embed_dev", "tn_lwe_keyswitch_dev",
     "tn_lwe_ksk_prepared_bytes", "tn_lwe_ksk_prepare_dev", "tn_lwe_keyswitch_prepared_dev",
     "tn_plan_export_table", "tn_ntt_forward_dev", "tn_ntt_inverse_dev",
     "tn_ntt_forward_host", "tn_ntt_inverse_host", "tn_ntt_forward_trace_host", "tn_twisted_ntt_forward_dev",
@@ -115,6 +117,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.tn_automorphism_dev.argtypes = [vp, vp, vp, sz, ctypes.POINTER(u32), sz, vp]
     lib.tn_automorphism_prepared_dev.argtypes = [vp, vp, vp, sz, ctypes.POINTER(u32), sz, vp]
     lib.tn_poly_galois_keyswitch_prepared_dev.argtypes = [vp, vp, u32, vp, sz, vp, sz, sz, u32, u32, vp]
+    lib.tn_poly_pack_step_prepared_dev.argtypes = [vp, vp, vp, u32, u32, vp, sz, vp, sz, sz, u32, u32, vp]
+    lib.tn_lwe_embed_dev.argtypes = [vp, vp, vp, sz, u32, vp]
     lib.tn_lwe_modswitch_dev.argtypes = [vp, vp, vp, sz, sz, vp]
     lib.tn_sample_extract_dev.argtypes = [vp, vp, vp, sz, u32, vp]
     lib.tn_lwe_keyswitch_dev.argtypes = [vp, vp, vp, vp, sz, sz, sz, sz, u32, u32, vp]
@@ -810,6 +814,123 @@ class Plan:
         c = self._lwe_out(out, (batch, self.n + 1), a.device)
         _check(self._lib, self._lib.tn_sample_extract_dev(self._h, a.data_ptr(), c.data_ptr(), batch, int(index), self._stream_ptr(stream)))
         return self._result(c, host, one, out)
+
+    def lwe_embed(self, lwe, index=0, out=None, stream=None):
+        """The RLWE ciphertext whose phase has the phase of an LWE ciphertext at coefficient `index` (tn_lwe_embed_dev), the exact
+        inverse of sample_extract at that index: lwe is (batch, n + 1), or (n + 1,) for one, under the coefficients of the ring key;
+        returns (batch, 2, n), or (2, n), with c1[k] = lwe[index - k] for k <= index, -lwe[n + index - k] above it, and c0 the
+        body at coefficient `index`, 0 elsewhere, all mod q.  The other coefficients of the phase are not zero: pack_lwes removes
+        them.  Host values or a device tensor in, the same kind out.  Works on every plan."""
+        x, host, one = self._lwe_in(lwe, "lwe", self.n + 1)
+        batch = int(x.shape[0])
+        if not 0 <= int(index) < 2 ** 32:
+            raise ValueError(f"Expected an index below n = {self.n}, got {index}")
+        c = self._lwe_out(out, (batch, 2, self.n), x.device)
+        _check(self._lib, self._lib.tn_lwe_embed_dev(self._h, x.data_ptr(), c.data_ptr(), batch, int(index), self._stream_ptr(stream)))
+        if host:
+            res = self.to_host(c.reshape(batch * 2, self.n)).reshape(batch, 2, self.n)
+            return res[0] if one else res
+        return self._result(c, host, one, out)
+
+    def poly_pack_step_prepared(self, ev, od, rot, galois, prepared: PreparedOperand, terms, base_log, balanced=False, out=None, stream=None):
+        """One level of the LWE -> RLWE packing tree from ONE launch (tn_poly_pack_step_prepared_dev):
+        c = (ev + X^rot od) + EvalAuto(ev - X^rot od, galois), that is, with t = X^rot od, s = ev + t, d = ev - t on both components,
+        c[r][0] = s0 + sigma_g(d0) + sum_j digit_j(sigma_g(d1)) * b[r][0][j], c[r][1] = s1 + sum_j digit_j(sigma_g(d1)) * b[r][1][j].
+        od=None is the trace step, c = ev + EvalAuto(ev, galois) (rot must be 0).  ev and od are (batch, 2, n), or (2, n) for one
+        ciphertext, host values or device tensors (both of one kind); rot is an integer below 2n, galois one odd integer below 2n;
+        the prepared operand is poly_galois_keyswitch_prepared's.  Returns (batch, 2, n) or (2, n), bit-identical to monomial_mul on
+        od, the sum and the difference mod q, poly_galois_keyswitch_prepared on the difference and the addition of the sum.
+        out must not overlap ev or od."""
+        import torch
+        self._own_prepared(prepared, "poly_pack_step_prepared", "key")
+        host = not _is_torch(ev)
+        if od is not None and _is_torch(od) == host:
+            raise TypeError("poly_pack_step_prepared: ev and od must both be host values or both device tensors")
+
+        def rows(x, name):
+            if host:
+                x = np.asarray(x)
+            if x.ndim not in (2, 3) or x.shape[-1] != self.n or x.shape[-2] != 2:
+                raise ValueError(f"Expected {name} of shape (batch, 2, {self.n}) or (2, {self.n})")
+            one_, batch_ = x.ndim == 2, (1 if x.ndim == 2 else int(x.shape[0]))
+            if host:
+                x = self.to_device(x.reshape(batch_ * 2, self.n))
+            else:
+                if not x.is_contiguous():
+                    raise TinyNttError(TN_EINVAL, f"{name}: need a contiguous tensor of {self.elem_bytes}-byte integers")
+                self._dev_rows(x.reshape(batch_ * 2, self.n), name)
+            return x, one_, batch_
+
+        ev, one, batch = rows(ev, "ev")
+        if od is not None:
+            od, one_od, batch_od = rows(od, "od")
+            if (one_od, batch_od) != (one, batch):
+                raise ValueError("Expected od of the shape of ev")
+        terms, g, rot = int(terms), int(galois), int(rot)
+        if terms < 1:
+            raise ValueError(f"Expected terms >= 1, got {terms}")
+        if not 0 <= g < 2 ** 32:
+            raise ValueError(f"Expected a Galois element below 2n = {2 * self.n}, got {g}")
+        if not 0 <= rot < 2 ** 32:
+            raise ValueError(f"Expected a rotation below 2n = {2 * self.n}, got {rot}")
+        sets = self._sets(prepared, batch, 2 * terms, "key")
+        c = out if out is not None else torch.empty((batch, 2, self.n), dtype=self.torch_dtype, device=ev.device)
+        if not _is_torch(c) or c.numel() != batch * 2 * self.n or not c.is_contiguous():
+            raise ValueError(f"Expected an output of {batch} x 2 rows of {self.n} coefficients")
+        self._dev_rows(c.reshape(batch * 2, self.n), "out")
+        _check(self._lib, self._lib.tn_poly_pack_step_prepared_dev(self._h, ev.data_ptr(), od.data_ptr() if od is not None else None, rot, g,
+                                                                   prepared.tensor.data_ptr(), sets, c.data_ptr(), batch, terms, int(base_log),
+                                                                   GADGET_BALANCED if balanced else 0, self._stream_ptr(stream)))
+        return self._result(c.reshape(batch, 2, self.n) if host else c, host, one, out)
+
+    def pack_lwes(self, lwe, keys: PreparedOperand, terms, base_log, balanced=False, stream=None):
+        """LWE -> RLWE ring packing (PackLWEs and the field trace of Chen, Dai, Kim, Song, "Efficient Homomorphic Conversion Between
+        (Ring) LWE Ciphertexts"): lwe is a device tensor (groups, count, n + 1), count a power of two <= n, LWE ciphertexts of
+        dimension n under the coefficients of the ring key s.  Returns a device tensor (groups, 2, n): RLWE ciphertexts whose phase is
+            n * sum_j mu_j X^(j n / count)   (plus noise),
+        mu_j the phase of lwe[:, j].  THE FACTOR n IS NOT REMOVED: every automorphism step doubles the kept coefficients, log2 n
+        steps in all.  A caller who wants sum_j mu_j X^(j n / count) scales the inputs (or the messages) by n^-1 mod q first, as the
+        paper does; the library does not.
+        keys: a PreparedOperand of log2(n) * 2 * terms rows; rows [(t - 1) * 2 * terms, t * 2 * terms), t = 1 .. log2 n, hold the
+        key from sigma_g(s) to s for g = 2^t + 1 ([2][terms] prepared rows, poly_galois_keyswitch_prepared's layout), shared by every
+        row.  All log2 n keys are needed for every count (numtheory.pack_elements lists k_t and g_t).
+        The steps: the rows go slot-major (count, groups); lwe_embed at index 0; log2(count) poly_pack_step_prepared launches on
+        halving batches (level t pairs the first half of the list with the second, rot = n / 2^t, g = 2^t + 1); then
+        log2(n / count) trace launches (od=None).  Nothing synchronises; temporaries come from torch's allocator.
+        stream: None (torch's current stream), a torch.cuda.Stream or a raw HIP stream handle; the library's launches are enqueued
+        on it and the method's own torch work (the slot-major copy, every level's allocation and the release of the level before)
+        runs under the same stream, so everything is ordered on it, as in Plan.bootstrap.  lwe and keys must be ready on that
+        stream.  The plan's own stream ("plan") is refused: torch cannot run on it."""
+        import torch
+        if isinstance(stream, str):
+            raise ValueError("pack_lwes: stream must be None, a torch.cuda.Stream or a raw stream handle (torch cannot run on the plan's own stream)")
+        if stream is not None:
+            ts = stream if isinstance(stream, torch.cuda.Stream) else torch.cuda.ExternalStream(int(stream), device=self.device)
+            with torch.cuda.stream(ts):
+                return self.pack_lwes(lwe, keys, terms, base_log, balanced, stream=None)
+        self._own_prepared(keys, "pack_lwes", "key")
+        if not _is_torch(lwe) or lwe.dim() != 3 or int(lwe.shape[2]) != self.n + 1:
+            raise ValueError(f"Expected lwe as a device tensor of shape (groups, count, {self.n + 1})")
+        groups, count, terms = int(lwe.shape[0]), int(lwe.shape[1]), int(terms)
+        if count < 1 or count & (count - 1) or count > self.n or groups < 1:
+            raise ValueError(f"Expected groups >= 1 and count a power of two between 1 and n = {self.n}, got {groups} and {count}")
+        if terms < 1:
+            raise ValueError(f"Expected terms >= 1, got {terms}")
+        elements = numtheory.pack_elements(self.n)
+        key = 2 * terms
+        if keys.rows != len(elements) * key:
+            raise ValueError(f"Expected keys of {len(elements)} x {key} rows, got {keys.rows}")
+        slot_major = lwe.transpose(0, 1).contiguous().reshape(count * groups, self.n + 1)
+        cur = self.lwe_embed(slot_major, 0, stream=stream)                    # (count * groups, 2, n): slot j at rows [j * groups, (j + 1) * groups)
+        for t, (k, g) in enumerate(elements, start=1):
+            level_key = PreparedOperand(self, keys.tensor[(t - 1) * key:t * key], key)
+            rows = int(cur.shape[0])
+            if rows > groups:                                                 # a pack level: the first half with the second
+                half = rows // 2
+                cur = self.poly_pack_step_prepared(cur[:half], cur[half:], k, g, level_key, terms, base_log, balanced, stream=stream)
+            else:                                                             # a trace step
+                cur = self.poly_pack_step_prepared(cur, None, 0, g, level_key, terms, base_log, balanced, stream=stream)
+        return cur
 
     def lwe_keyswitch(self, lwe, ksk, n_out, terms, base_log, balanced=False, out=None, stream=None):
         """The LWE-to-LWE key switch (tn_lwe_keyswitch_dev): lwe is (batch, n_in + 1), ksk is (n_in, terms, n_out + 1) words of the

@@ -54,6 +54,16 @@ def galois_element(n: int, step: int = 0, conjugate: bool = False) -> int:
     return g
 
 
+def pack_elements(n: int):
+    """The levels of LWE -> RLWE packing and of the trace in Z_q[x]/(x^n + 1) (Plan.pack_lwes): [(k_t, g_t)] for t = 1 .. log2 n
+    with the rotation k_t = n / 2^t and the Galois element g_t = 2^t + 1 (the last one is n + 1).  Level t's key, from
+    sigma_{g_t}(s) to s, is entry t - 1 of the key list."""
+    n = int(n)
+    if n < 2 or n & (n - 1):
+        raise ValueError(f"Expected n a power of two, at least 2, got {n}")
+    return [(n >> t, (1 << t) + 1) for t in range(1, n.bit_length())]
+
+
 def psi_from_omega(omega: int, n: int, q: int) -> int:
     """A primitive 2n-th root psi with psi^2 == omega (needed because plans are keyed on psi).
 
